@@ -210,6 +210,29 @@ def traffic_child_args(a):
             "--n-importance", str(a.n_importance), "--micro-batch", str(a.micro_batch)] + (["--so", a.so] if a.so else [])
 
 
+DUMP_MAX_BYTES = 64 << 20
+
+
+def dump_outputs(d, arrays):
+    """--dump-outputs: each tensor of `arrays` as d/<name>.npy in float32 (float64 stays float64).  Over DUMP_MAX_BYTES in all,
+    each array of more than one row keeps the same share of its rows, a fixed sample (numpy default_rng(0), in row order): the
+    same rows in every run of the same arguments."""
+    import numpy as np
+    host = {}
+    for name, t in arrays.items():
+        t = t.detach()
+        host[name] = t.cpu().numpy().astype(np.float64 if t.dtype == torch.float64 else np.float32).reshape(t.shape or (1,))
+    total = sum(x.nbytes for x in host.values())
+    if total > DUMP_MAX_BYTES:
+        keep = DUMP_MAX_BYTES / total
+        for name, x in host.items():
+            if x.shape[0] > 1:
+                host[name] = x[np.sort(np.random.default_rng(0).choice(x.shape[0], max(1, int(x.shape[0] * keep)), replace=False))]
+    os.makedirs(d, exist_ok=True)
+    for name, x in host.items():
+        np.save(os.path.join(d, name + ".npy"), x)
+
+
 CONFIGS = {   # BASELINE.json configs (SURVEY 8d): input rays per GPU, N_samples, N_importance, blur kernel on, micro-batch
     "C1": dict(n_rand=256, ns=32, ni=0, kernel=False, micro=0),
     "C2": dict(n_rand=4096, ns=64, ni=64, kernel=True, micro=0),
@@ -270,9 +293,15 @@ def main():
                     help="BASELINE config timed as the headline workload (C2 = the one the metric is quoted on)")
     ap.add_argument("--extra", type=str, default=None, help="other BASELINE configs reported under extra_configs "
                     "(default at 1 GPU: C1,C3,C5,eval; none on multi-GPU runs); empty to skip")
+    ap.add_argument("--dump-outputs", type=str, default=None, metavar="DIR", help="after the timed steps, write what the headline's "
+                    "last timed step computed (rank 0: `loss`; init_* = the same step from the seeded initial model: its loss, render "
+                    "outputs and MLP gradient) as DIR/<name>.npy, float32, so that two builds run with the same arguments can be compared "
+                    "array by array (main: dump_init_step)")
     a = ap.parse_args()
     if a.gpus < 1:
         raise SystemExit("--gpus must be >= 1")
+    if a.steps < 1:
+        raise SystemExit("--steps must be >= 1")
     if a.config != "C2":
         c = CONFIGS[a.config]
         a.n_rand, a.n_samples, a.n_importance = c["n_rand"], c["ns"], c["ni"]
@@ -341,15 +370,34 @@ def main():
     def evals_per_step(n_rand, ns, ni, kernel=True):
         return n_rand * (M if kernel else 1) * (ns + (ns + ni if ni else 0))
 
-    def run_mode(pf, pb, steps, warmup, cfg=None, sustained_s=0.0, variant=None, trained_like=False):
+    def make_trainer(net, cfg):
+        return Trainer(net, synth.H_DEF, synth.W_DEF, synth.FOCAL_DEF, cfg["ns"], cfg["ni"], kernel_start_iter=0,
+                       allkernel_start_iter=1 << 30, distributed=True, micro_batch=cfg["micro"])
+
+    def step_outputs(tr, net, batch, i):
+        """One Trainer.step, returning what it returns (the loss) and what its model calls returned (one per micro-batch slice):
+        the blurred and sharp colours of both passes and the noise branch's colour."""
+        calls = []
+        hook = net.register_forward_hook(lambda m, inp, out: calls.append([o.detach() if isinstance(o, torch.Tensor) else None for o in out]))
+        try:
+            loss = tr.step(batch, i)
+        finally:
+            hook.remove()
+        arrays = {"loss": loss}
+        for name, k in (("rgb_blur", 0), ("rgb0_blur", 1), ("noise", 3), ("rgb", 5), ("rgb0", 6)):
+            if calls[0][k] is not None:
+                arrays[name] = torch.cat([c[k] for c in calls])
+        return arrays
+
+    def run_mode(pf, pb, steps, warmup, cfg=None, sustained_s=0.0, variant=None, trained_like=False, dump=None):
         """Time `steps` optimisation steps of one BASELINE config in one precision mode (max over ranks).  sustained_s > 0: after
         the timed region, the same steps back to back for at least that many seconds (the timed region of the driver's
-        `--steps 20` is a third of a second on a chip that runs at its power cap: this is its steady-state neighbour)."""
+        `--steps 20` is a third of a second on a chip that runs at its power cap: this is its steady-state neighbour).
+        dump: directory for --dump-outputs -- the loss the last timed step returned is written there."""
         cfg = cfg or dict(n_rand=a.n_rand, ns=a.n_samples, ni=a.n_importance, kernel=True, micro=a.micro_batch)
         batches = make_batches(cfg["n_rand"])
         net = make_model(model_args(cfg["ni"]), dev, ops.Precision(pf, pb, a.variant if variant is None else variant), trained_like=trained_like)
-        tr = Trainer(net, synth.H_DEF, synth.W_DEF, synth.FOCAL_DEF, cfg["ns"], cfg["ni"], kernel_start_iter=0,
-                     allkernel_start_iter=1 << 30, distributed=True, micro_batch=cfg["micro"])
+        tr = make_trainer(net, cfg)
         if trained_like:
             # The density field is HELD: every kernel of the step runs (both marches, loss, backward, all-reduce, Adam), Adam with a
             # zero rate.  From fresh Adam moments the first updates are +-lrate whatever the gradient, and through the x3000 density
@@ -374,7 +422,8 @@ def main():
         tr.allreduce_events = []
         t0 = time.perf_counter()
         for i in range(steps):
-            tr.step(batches[(warmup + i) % n_batches], warmup + i)
+            last_step = (warmup + i, net.hooks.draw_offset)      # (host values: what dump_init_step replays the last step with)
+            loss = tr.step(batches[(warmup + i) % n_batches], warmup + i)
         sync()
         dt = time.perf_counter() - t0
         ar_ms = sum(a_.elapsed_time(b_) for a_, b_ in tr.allreduce_events) / max(len(tr.allreduce_events), 1)
@@ -386,6 +435,9 @@ def main():
                                                "coarse": round(cl / ca, 4) if ca else None}
         live = live_share(live0, tr.live_counts())
         dense_steps = int(getattr(tr, "_dense_steps", 0)) if getattr(tr, "_dense_now", False) else 0      # (what the trainer's policy chose)
+        if dump and rank == 0:
+            dump_outputs(dump, {"loss": loss})
+        del loss
         # kernel groups: the SAME steps once more (state restored) with HIP events around each MLP kernel group on the launch stream.
         # The timed region above runs the march as one C-ABI call per direction (lush_march_fwd / lush_march_bwd); with the timer set
         # the same kernels are launched group by group through the piecewise entry points.
@@ -435,7 +487,30 @@ def main():
         summ["_sustained"] = sustained
         summ["_live"] = live
         summ["_dense_steps"] = dense_steps
+        summ["_last_step"] = last_step
         return dt, summ
+
+    def dump_init_step(pf, pb, i, draw_offset, d):
+        """--dump-outputs, init_*: the last timed step (its batch, step number, Philox draws, mode and kernels) run from the seeded
+        initial model by a fresh trainer -- its loss, render outputs and the coarse + fine MLPs' flat gradient (forward, backward,
+        all-reduce).  The timed steps' own state is not comparable between runs: the weight gradients are summed with float atomics,
+        Adam turns a rounding-level difference of a near-zero gradient into a +-lrate step of that parameter, and the sharp field
+        carries it on (two runs of one build: the last timed step's colours 1.4e-2 apart, its loss 1.8e-5).  From the seeded model
+        the step's inputs are the same in every run, so two runs agree on it to the rounding of one step.  The blur kernel network's
+        gradients are left out: atomic sums over every ray that cancel to a few 1e-5 of their terms, their rounding is their size."""
+        cfg = dict(n_rand=a.n_rand, ns=a.n_samples, ni=a.n_importance, kernel=True, micro=a.micro_batch)
+        batch = make_batches(cfg["n_rand"])[i % n_batches]
+        net = make_model(model_args(cfg["ni"]), dev, ops.Precision(pf, pb, a.variant))
+        tr = make_trainer(net, cfg)
+        net.hooks.draw_offset = draw_offset
+        arrays = step_outputs(tr, net, batch, i)
+        sync()
+        if rank == 0:
+            a0, b0 = tr.flat.segments[0]          # (adam_segments: the coarse and fine MLPs)
+            arrays["grad_mlp"] = tr.flat.grad[a0:b0]
+            dump_outputs(d, {"init_" + k: v for k, v in arrays.items()})
+        del tr, net, batch, arrays
+        torch.cuda.empty_cache()
 
     def run_c1(pf, pb, steps, warmup):
         """BASELINE config 1 (N_rand 256, 32+0, naive): NeRFAll.forward cannot take N_importance = 0 (it indexes
@@ -525,7 +600,9 @@ def main():
     pf, pb = ops.parse_planes(a.planes)
     evals_step = evals_per_step(a.n_rand, a.n_samples, a.n_importance)
     progress(f"headline mode {a.planes}: {a.warmup} warm-up + {a.steps} timed steps on {world} rank(s)")
-    dt, groups = run_mode(pf, pb, a.steps, a.warmup, sustained_s=a.sustained)
+    dt, groups = run_mode(pf, pb, a.steps, a.warmup, sustained_s=a.sustained, dump=a.dump_outputs)
+    if a.dump_outputs:
+        dump_init_step(pf, pb, *groups["_last_step"], a.dump_outputs)
     progress(f"headline: {dt / a.steps * 1e3:.2f} ms/step" + (f"; sustained {groups['_sustained']['ms_per_step']:.2f} ms/step over "
                                                                f"{groups['_sustained']['seconds']:.1f} s" if groups.get("_sustained") else ""))
     # the same configuration with the backward over ALL the points (LUSH_VARIANT_DENSE_BWD: rounds 1-4; what the step costs

@@ -311,6 +311,33 @@ def test_bench_refuses_wrong_world(tmp_path):
     assert r.returncode != 0 and "WORLD_SIZE=2" in (r.stdout + r.stderr) and '"metric"' not in r.stdout
 
 
+def test_bench_dump_outputs_writes_float_arrays(tmp_path, monkeypatch):
+    """--dump-outputs DIR: one DIR/<name>.npy per array, float32 (float64 kept), a 0-d loss as one element; over the byte budget
+    a fixed sample of rows, the same in every call."""
+    import importlib
+    sys.path.insert(0, ROOT)
+    bench = importlib.import_module("bench")
+    d = tmp_path / "out"
+    bench.dump_outputs(str(d), {"loss": torch.tensor(0.25), "params": torch.arange(6, dtype=torch.float16).reshape(2, 3),
+                                "grad": torch.ones(4, dtype=torch.float64)})
+    loss, params, grad = (np.load(d / f"{n}.npy") for n in ("loss", "params", "grad"))
+    assert loss.dtype == np.float32 and loss.tolist() == [0.25]
+    assert params.dtype == np.float32 and params.shape == (2, 3) and params[1, 2] == 5.0
+    assert grad.dtype == np.float64 and grad.shape == (4,)
+    big = {"rows": torch.arange(4000, dtype=torch.float32).reshape(1000, 4), "loss": torch.tensor(1.0)}
+    monkeypatch.setattr(bench, "DUMP_MAX_BYTES", 4000)
+    for sub in ("big1", "big2"):
+        bench.dump_outputs(str(tmp_path / sub), big)
+    r1, r2 = (np.load(tmp_path / sub / "rows.npy") for sub in ("big1", "big2"))
+    assert 200 < r1.shape[0] <= 250 and r1.shape[1] == 4 and np.array_equal(r1, r2)      # <= the budget, the same rows each time
+    assert np.all(np.diff(r1[:, 0]) > 0) and np.all(r1[:, 0] % 4 == 0)      # whole rows, in row order
+    assert np.load(tmp_path / "big1" / "loss.npy").tolist() == [1.0]
+    # the option parses (the run then stops at the --gpus check, before anything touches a device)
+    r = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--dump-outputs", str(tmp_path / "x"), "--gpus", "0"],
+                       capture_output=True, text=True, timeout=300)
+    assert "--gpus must be >= 1" in (r.stderr + r.stdout), r.stderr[-400:]
+
+
 def test_trainer_lr_follows_reference_loop():
     """run_lushnerf.py:675-685, 788: step g runs with the rate computed from global_step g-1."""
     from oracle import lush_oracle as O

@@ -700,6 +700,41 @@ def test_bench_two_ranks_rehearsal(diag, tmp_path, ranks):
     print(f"bench.py --gpus {ranks} rehearsed on one GPU: {d['ms_per_step']} ms/step of {ranks} time-shared ranks, all-reduce {d['allreduce_ms']} ms over gloo")
 
 
+def test_bench_dump_outputs(diag, tmp_path):
+    """bench.py --dump-outputs on a small headline run: the last timed step's loss, and the same step from the seeded model (init_*):
+    its loss, render outputs (model tuple entries 0, 1, 3, 5, 6: one row per input ray) and the coarse + fine MLPs' gradient --
+    float32, finite; the last timed step ran on the trained state (its loss is not the seeded model's), the timed region is the one
+    --steps asked for."""
+    import json, os, subprocess, sys
+    import numpy as np
+    from lush_nerf_amd.trainer import adam_segments
+    root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+    env = dict(os.environ)
+    for k in ("RANK", "LOCAL_RANK", "WORLD_SIZE", "MASTER_PORT"):
+        env.pop(k, None)
+    out = tmp_path / "dump"
+    r = subprocess.run([sys.executable, os.path.join(root, "bench.py"), "--gpus", "1", "--steps", "2", "--warmup", "2", "--n-rand", "256",
+                        "--no-cpu-baseline", "--also=", "--extra=", "--no-traffic", "--sustained", "0", "--no-dense", "--dump-outputs", str(out)],
+                       capture_output=True, text=True, timeout=300, env=env, cwd=str(tmp_path))
+    assert r.returncode == 0, r.stdout[-1500:] + r.stderr[-3000:]
+    d = json.loads([l for l in r.stdout.splitlines() if l.startswith("{")][0])
+    assert d["steps"] == 2 and d["ms_per_step"] > 0
+    names = ["loss"] + ["init_" + n for n in ("loss", "rgb_blur", "rgb0_blur", "noise", "rgb", "rgb0", "grad_mlp")]
+    assert sorted(os.listdir(out)) == sorted(n + ".npy" for n in names)
+    arr = {f[:-4]: np.load(out / f) for f in os.listdir(out)}
+    import argparse
+    from lush_nerf_amd import model as M
+    args = argparse.Namespace(blur_model_type="dpnerf", multires=10, multires_views=4, i_embed=0, use_viewdirs=True, N_importance=64, netdepth=8,
+                              netwidth=256, netdepth_fine=8, netwidth_fine=256, rgb_activate="sigmoid", sigma_activate="relu",
+                              tone_mapping_type="gamma", render_rmnearplane=80)
+    n_mlp = sum(p.numel() for p in adam_segments(M.NeRFAll(args, M.RBK(30, 64, 4, 64, 1, 32, 1, 32, 1, 32, 3, 3, [4], True, 0.1, 4)))[0])
+    for k, v in arr.items():
+        assert v.dtype == np.float32 and bool(np.isfinite(v).all()), k
+        assert v.shape == ((1,) if k.endswith("loss") else (n_mlp,) if k == "init_grad_mlp" else (256, 3)), (k, v.shape)
+    assert float(np.abs(arr["init_grad_mlp"]).max()) > 0 and float(np.abs(arr["init_rgb"]).max()) > 0
+    assert arr["loss"][0] != arr["init_loss"][0]
+
+
 @pytest.mark.parametrize("kernel_on", [True, False])
 def test_step_graph_matches_the_eager_step(diag, kernel_on):
     """Trainer.step_graph -- the whole step captured in a HIP graph, with the learning rate, Adam's step counts and the Philox

@@ -12,6 +12,8 @@ from oracle import lush_oracle as O
 from tests import util
 
 TOL = 2e-5
+# every test here runs on MKL's reproducible code path (tests/conftest.py): the path the fixtures were generated on
+pytestmark = pytest.mark.mkl_reproducible
 
 
 def _batch(n, seed):
