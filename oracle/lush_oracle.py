@@ -148,7 +148,7 @@ def sample_pdf(bins: Tensor, weights: Tensor, n_samples: int, det: bool,
     cdf = torch.cumsum(pdf, -1)
     cdf = torch.cat([torch.zeros_like(cdf[..., :1]), cdf], -1)
     if det:
-        u = torch.linspace(0., 1., steps=n_samples).to(cdf.dtype).expand(list(cdf.shape[:-1]) + [n_samples])
+        u = torch.linspace(0., 1., steps=n_samples, device=cdf.device).to(cdf.dtype).expand(list(cdf.shape[:-1]) + [n_samples])
     elif u is None:
         u = torch.rand(list(cdf.shape[:-1]) + [n_samples])
     u = u.contiguous().to(cdf.dtype)
@@ -165,7 +165,7 @@ def sample_pdf(bins: Tensor, weights: Tensor, n_samples: int, det: bool,
 
 # --------------------------------------------------------------------------- a8/a9/a10
 def _z_grid(near: Tensor, far: Tensor, n: int, lindisp: bool) -> Tensor:
-    t = torch.linspace(0., 1., steps=n).to(near.dtype)
+    t = torch.linspace(0., 1., steps=n, device=near.device).to(near.dtype)
     if not lindisp:
         z = near * (1. - t) + far * t
     else:

@@ -459,6 +459,96 @@ def case_trajectory_long(seed=43, n_rand=32, steps=300):
          final_rgb_b=sd["mlp_fine.rgb_linear.bias"].numpy().copy())
 
 
+def case_trajectory_trained_like(seed=0, n_rand=32, steps=60):
+    """A training run of the reference from the density field bench.py's `trained_like` workload starts from
+    (synth.all_weights(trained_like=True), seed 0: the calibrated one) -- empty space and surfaces behind a x3000 density
+    head, where the derivative with respect to the ray geometry, and so every gradient of the blur-kernel (RBK) network, is
+    a cancelling sum.  The RBK network learns only through d(rays) (models/lushnerf.py:639-654).
+    Targets: what a fixed teacher -- the trained-like weight set of seed + 100, at the same rbk_scale -- renders for the same
+    rays without jitter or density noise (as case_trajectory_long).  A teacher with the student's NeRF weights and only
+    another blur kernel gives no signal here: this field renders a nearly flat image (colour std 5e-3 over a batch), another
+    RBK moves the targets by 8e-5, no more than the student's own jitter and density noise (step-0 loss 1.0e-4 against 6.8e-5
+    with the student's own RBK), and such a run's loss only rises as Adam's first steps move the NeRF (1.1e-3 at step 10).
+    With the whole teacher the step-0 loss is 1e-2; the RBK tensors still move by ~lr per step under Adam, and the direction
+    they move in is decided by d(rays) through the sharp field.  Blur kernel on (allkernel=False, kernel_pixel from the
+    batch); optimizer set-up, lr rule and fresh rays / draws every step as case_trajectory_long.  Stores the targets, the loss curve, the final parameter norms, the final
+    fine rgb head and every mlp_rbk.* tensor in full ("rbk.<name>").
+    The same run in float64 -- the oracle (oracle/lush_oracle.py) on float64 inputs, torch.optim.Adam in float64, the same
+    draws, targets and lr rule -- is stored beside it (losses_f64, "f64.<name>", final_rgb_w_f64, final_norms_f64): how far the reference's
+    own fp32 run lands from float64 is the chaos floor of this regime, which the GPU test's gates are built on."""
+    from oracle import lush_oracle as O
+    Ns = Ni = 64
+    w0 = synth.all_weights(NUM_IMG, seed, rbk_scale=2.0e4, trained_like=True)
+    net = build_ref(Ni, w0)
+    teacher = build_ref(Ni, synth.all_weights(NUM_IMG, seed + 100, rbk_scale=2.0e4, trained_like=True))
+    net.train()
+    teacher.train()
+    noise = list(net.mlp_noise_coarse.parameters())
+    ids = set(map(id, noise))
+    base = [p for p in net.parameters() if id(p) not in ids]
+    lrate, decay = 5e-4, 250
+    opt = torch.optim.Adam([{"params": base}, {"params": noise, "lr": lrate}], lr=lrate)
+    kw = dict(perturb=1., N_importance=Ni, N_samples=Ns, use_viewdirs=True, white_bkgd=False, raw_noise_std=1.,
+              inference=False, near=0., far=1.)
+    kw_t = dict(kw, perturb=0., raw_noise_std=0.)
+    losses, targets, global_step = [], [], 0
+    for s in range(steps):
+        b = synth.ray_batch(n_rand, seed, NUM_IMG, step=s)
+        d = synth.draws(n_rand * 5, Ns, Ni, seed, step=s)
+        rays = torch.from_numpy(b["rays"])
+        info = {"images_idx": torch.from_numpy(b["images_idx"])}
+        mask = torch.from_numpy(b["fq_mask"]).bool()
+        with torch.no_grad():
+            target = teacher(H, W, K, chunk=1 << 20, rays=rays, rays_info=info, retraw=True, force_naive=False, allkernel=False,
+                             kernel_pixel=mask, **kw_t)[0].clone()
+        with ServeDraws([d["t_rand"], d["noise_c"], d["u"], d["noise_f"]]):
+            out = net(H, W, K, chunk=1 << 20, rays=rays, rays_info=info, retraw=True, force_naive=False, allkernel=False,
+                      kernel_pixel=mask, **kw)
+        loss = ref_helpers.img2mse(out[0], target) * 0.5 + ref_helpers.img2l1(out[0], target) * 0.5 \
+            + ref_helpers.img2mse(out[1], target) * 0.5 + ref_helpers.img2l1(out[1], target) * 0.5
+        opt.zero_grad()
+        loss.backward()
+        opt.step()
+        new_lrate = lrate * (0.1 ** (global_step / (decay * 1000)))
+        for g in opt.param_groups:
+            g["lr"] = new_lrate
+        global_step += 1
+        losses.append(loss.item())
+        targets.append(target.numpy().copy())
+        if s % 10 == 0:
+            print("trained-like traj step", s, loss.item(), flush=True)
+    sd = {canon_name(k): v for k, v in net.state_dict().items()}
+    # the float64 counterpart: the oracle, the same draws and targets, torch Adam (one group: both of the reference's have the same rate)
+    p64 = {k: torch.from_numpy(v.astype(np.float64)).requires_grad_(True) for k, v in w0.items()}
+    opt64 = torch.optim.Adam(list(p64.values()), lr=lrate)
+    losses64 = []
+    for s in range(steps):
+        b = synth.ray_batch(n_rand, seed, NUM_IMG, step=s)
+        d = {k: torch.from_numpy(v.astype(np.float64)) for k, v in synth.draws(n_rand * 5, Ns, Ni, seed, step=s).items()}
+        out = O.forward_train(p64, H, W, FOCAL, torch.from_numpy(b["rays"]).double(), torch.from_numpy(b["images_idx"]), Ns, Ni,
+                              force_naive=False, allkernel=False, kernel_pixel=torch.from_numpy(b["fq_mask"]), draws=d)
+        loss = O.train_loss(out[0], out[1], torch.from_numpy(targets[s]).double())
+        opt64.zero_grad()
+        loss.backward()
+        opt64.step()
+        for g in opt64.param_groups:
+            g["lr"] = O.lr_at(s, lrate, decay)
+        losses64.append(loss.item())
+        if s % 10 == 0:
+            print("trained-like traj float64 step", s, loss.item(), flush=True)
+    rbk = sorted(k for k in w0 if k.startswith("mlp_rbk."))
+    alias = {"dbk_view_embedding.view_embed_layer.weight": "mlp_rbk.view_embedding_layer.view_embed_layer.weight"}
+    save("train_trajectory_trained_like", meta=np.array([n_rand, Ns, Ni, seed, steps]), losses=np.array(losses),
+         targets=np.stack(targets).astype(np.float32),
+         final_norms=np.array([float(sd[k].double().norm()) for k in sorted(sd)]), final_keys=np.array(sorted(sd)),
+         final_rgb_w=sd["mlp_fine.rgb_linear.weight"].numpy().copy(),
+         final_rgb_b=sd["mlp_fine.rgb_linear.bias"].numpy().copy(),
+         losses_f64=np.array(losses64), final_rgb_w_f64=p64["mlp_fine.rgb_linear.weight"].detach().numpy().copy(),
+         final_norms_f64=np.array([float(p64[alias.get(k, k)].detach().norm()) for k in sorted(sd)]),
+         **{"rbk." + k: sd[k].numpy().copy() for k in rbk},
+         **{"f64." + k: p64[k].detach().numpy().copy() for k in rbk})
+
+
 def _consist_tables(seed, V=5, ns=32, anchor=3):
     """Align_Matrix / Align_Mask of the consistency branch from the build-owned generator (as case_consistency)."""
     HW = H * W
@@ -563,6 +653,7 @@ def case_train_consist(seed=52, n_rand=12, Ns=64, Ni=64):
 
 NEW_CASES = {"sample_pdf_z": case_sample_pdf_z, "lindisp_white": case_lindisp_white, "eval_forward": case_eval_forward,
              "consistency": case_consistency, "trajectory": case_trajectory, "trajectory_long": case_trajectory_long,
+             "trajectory_trained_like": case_trajectory_trained_like,
              "train_c1": case_train_c1, "train_consist": case_train_consist}
 
 

@@ -817,9 +817,20 @@ MASKED_GATE = MASKED_FLOOR      # (name kept for the sections that only need the
 # float64 on d(rays) and on the blur-kernel network's tensors (the sharp reference fixtures: 1e-4 .. 1e-3), and one fp16 plane in
 # the forward sits at 13 .. 21 % there (16 x fp32's miss; 1 - cos 1.2e-2), two bf16 planes at 1.7 % (1 - cos 5.8e-5); the 8 x 256
 # networks' own tensors: median 9e-3 / 7e-5.  Gates of that regime = 2 .. 3 x what was measured (profiles/r06_trained_like_grads.md).
-MASKED_CAP_BY_TAG["trained-like regime"] = 5e-1
+# The cap is per mode there: a two-plane forward -- (2,h), (2,2) -- is held to ~3 x its measured worst tensor (1.7e-2, an RBK
+# tensor and d(rays), the same in both modes; (2,h) measured again: mlp_rbk.v_linear.bias 1.65e-2, 0.43 of the 5e-2 allowance), not to
+# the headline mode's 5e-1, which 32 x fp32's own 1 % miss would otherwise reach;
+# (h,h) keeps 5e-1 (worst measured 2.1e-1) -- whether its gradients there train alike is tested by
+# tests/test_gpu_parity.py::test_trained_like_trajectory_follows_the_reference.
+MASKED_CAP_BY_TAG["trained-like regime"] = {(ops.PLANES_F16, ops.PLANES_F16): 5e-1, (2, ops.PLANES_F16): 5e-2, (2, 2): 5e-2}
 COS_GATE_BY_TAG = {"trained-like regime": {(ops.PLANES_F16, ops.PLANES_F16): 3e-2, (2, ops.PLANES_F16): 3e-3, (2, 2): 2e-4}}
 WELL_FLOOR_BY_TAG = {"trained-like regime": {(ops.PLANES_F16, ops.PLANES_F16): 1.2e-2}}
+
+
+def masked_cap(tag):
+    """MASKED_CAP_BY_TAG[tag]: one figure, or one per mode (a mode it does not list keeps the largest)."""
+    cap = MASKED_CAP_BY_TAG.get(tag, MASKED_CAP)
+    return cap.get(tuple(E2E_PLANES), max(cap.values())) if isinstance(cap, dict) else cap
 
 
 def masked_grad_check(tag, run_oracle, gpu_grads, gpu_extra, keep, prec):
@@ -842,13 +853,13 @@ def masked_grad_check(tag, run_oracle, gpu_grads, gpu_extra, keep, prec):
     for k, got, t64, t32 in items:
         e_gpu, e_f32 = util.relerr(got, t64), util.relerr(t32, t64)
         PER_TENSOR.append((tag, k, e_gpu, e_f32))
-        excess = e_gpu / max(floor, min(MASKED_CAP_BY_TAG.get(tag, MASKED_CAP), factor * e_f32))
+        excess = e_gpu / max(floor, min(masked_cap(tag), factor * e_f32))
         if not excess <= worst_excess:          # NaN propagates
             worst_excess, worst = excess, (k, e_gpu, e_f32)
     ok = bool(worst_excess <= 1.0)
     RESULTS.append((f"{tag} MASKED grads vs float64 [{worst[0]}] (e_gpu / allowed)", worst_excess, 1.0, ok))
     print(f"{'ok  ' if ok else 'FAIL'} {tag} masked oracle: worst tensor {worst[0]}: e_gpu {worst[1]:.2e}, fp32 oracle {worst[2]:.2e}, "
-          f"allowed max({floor:.0e}, min({MASKED_CAP_BY_TAG.get(tag, MASKED_CAP):.1e}, {factor:.0f} x fp32)) -> {worst_excess:.2f} of the allowance", flush=True)
+          f"allowed max({floor:.0e}, min({masked_cap(tag):.1e}, {factor:.0f} x fp32)) -> {worst_excess:.2f} of the allowance", flush=True)
     # direction of every gradient tensor: cosine with the float64 oracle's.  A gate that does not scale with the mode's
     # element-wise allowance: whatever the operand width, a parameter tensor must be pushed the way float64 pushes it --
     # 0.999 with 16-bit operands in the backward, 0.999999 fp32-equivalent; tensors on which the fp32 oracle itself

@@ -69,9 +69,14 @@ def test_fp16_forward_mode(diag, monkeypatch):
 def test_outputs_stay_inside_the_bound_on_a_trained_like_field(diag):
     """The render outputs of the headline mode on the density field bench.py's `trained_like` workload starts from
     (synth.all_weights(trained_like=True): sigma = 3000 w.h + 20 -- empty space and surfaces, a x3000 density head that amplifies the
-    forward's operand rounding) and on one twice as sharp: the blurred and the sharp colours of both passes within the north star's 1e-4
-    of the fp32 oracle in (h,h) (measured 4.2e-5 / 5.3e-5: the initialisation's 1.2e-5 grows with the sharpness, the bound holds),
-    2e-5 in the strict mode -- where the fp32 oracle itself is 3e-6 / 2e-5 from float64 (tools/sharpness_parity.py prints the table)."""
+    forward's operand rounding) and on one twice as sharp (x6000): the blurred and the sharp colours of both passes against the fp32 oracle.
+    At 64 rays (320 marched): within the north star's 1e-4 in (h,h) (measured 4.2e-5 / 5.3e-5: the initialisation's 1.2e-5 grows with the
+    sharpness), 2e-5 in the strict mode -- where the fp32 oracle itself is 3e-6 / 2e-5 from float64 (tools/sharpness_parity.py prints the
+    table).  The bound is a maximum over the batch, and 64 rays do not reach the tail of its distribution: the leg at the bench's size
+    (_full_size_outputs, N_rand 4096 = 20 480 marched rays, against the oracle run on the GPU)
+    holds both fields to TL_FULL_BOUND_22 in (2,2) and (h,h) to 2.5e-4 with at most 4 of the 4 096 rays beyond 1e-4: there (h,h) leaves
+    the 1e-4 on one ray of the trained-like field and two of the x6000 one (test_headline_output_bound_at_the_bench_size, strict xfail).
+    The GPU fp32 oracle is checked against float64 first: the bound is defined against fp32 arithmetic."""
     import argparse
     from lush_nerf_amd import model as M, ops, synth
     from oracle import lush_oracle as O
@@ -101,6 +106,106 @@ def test_outputs_stay_inside_the_bound_on_a_trained_like_field(diag):
                 err = float((out[i].cpu() - ref[i]).abs().max() / ref[i].abs().max())
                 assert err < tol, (tl, name, oname, err)
             assert net.read_faults() == 0
+    r = _full_size_outputs()
+    # the oracle on the GPU is the fp32 computation: no reduced-precision matmul path in torch's GPU BLAS
+    assert r["check"]["gpu"] <= 2.0 * r["check"]["cpu"], r["check"]
+    for (tl, name), e in r["err"].items():
+        if name == "2,2":
+            assert max(e.values()) < TL_FULL_BOUND_22, (tl, name, e)
+        else:       # (h,h): "< 1e-4" is the strict xfail test_headline_output_bound_at_the_bench_size; what holds is this
+            assert max(e.values()) < 2.5e-4, (tl, name, e)
+            assert max(r["beyond"][tl, name].values()) <= 4, (tl, name, r["beyond"][tl, name])
+
+
+# At the bench's size (_full_size_outputs, 4 096 rays) against the fp32 oracle, measured: (2,2) 1.0e-4 (9.97e-5, the sharp rgb) on the
+# trained-like field and 6.3e-5 on the x6000 one; (h,h) 1.03e-4 (1 ray beyond 1e-4) / 1.06e-4 (2 rays).  The 64-ray leg's 2e-5 does not
+# hold at this size in the fp32-equivalent mode either, and it is not the mode's arithmetic: the fp32 oracle ITSELF is 9.98e-5 / 7.2e-5
+# from the float64 oracle there, further than (2,2) is (5.3e-5 / 4.8e-5; (h,h) 9.9e-5 / 1.24e-4).  The largest error sits on the few rays
+# where a fine sample lands next to one of sample_pdf's CDF knots behind a sharp surface, where a 1-ulp difference in the coarse weights
+# moves a sample by a whole bin.  The measurement requires a looser bound than 2e-5: 2 x the (2,2) figure measured.
+TL_FULL_BOUND_22 = 2e-4
+_FULL_SIZE = {}
+
+
+def _full_size_outputs():
+    """The leg of test_outputs_stay_inside_the_bound_on_a_trained_like_field at the bench's size (N_rand 4096, blur kernel on: 20 480
+    marched rays, tools/sharpness_fullsize.py's size), computed once per session: the four colours of (h,h) and (2,2) against the fp32
+    oracle run on the GPU (the CPU oracle takes minutes here), normalised as the 64-ray leg does -- per output the largest error over the
+    batch / the largest value -- and per output the number of rays (largest error over their 3 channels) beyond 1e-4.  And the check that
+    the GPU oracle is the fp32 computation: on the initialisation field, on the batch's first 128 rays, its largest distance from the GPU
+    float64 oracle over the four outputs ("gpu") against the CPU fp32 oracle's from the CPU float64 one on the same rays ("cpu")."""
+    if _FULL_SIZE:
+        return _FULL_SIZE
+    import argparse
+    from lush_nerf_amd import model as M, ops, synth
+    from oracle import lush_oracle as O
+    from tests import util
+    dev = torch.device("cuda:0")
+    H, W, F, n_img, n, Ns, Ni, m = synth.H_DEF, synth.W_DEF, synth.FOCAL_DEF, 30, 4096, 64, 64, 128
+    args = argparse.Namespace(blur_model_type="dpnerf", multires=10, multires_views=4, i_embed=0, use_viewdirs=True, N_importance=Ni, netdepth=8,
+                              netwidth=256, netdepth_fine=8, netwidth_fine=256, rgb_activate="sigmoid", sigma_activate="relu",
+                              tone_mapping_type="gamma", render_rmnearplane=80)
+    b = {k: torch.from_numpy(v) for k, v in synth.ray_batch(n, 1000, n_img).items()}
+    d = {k: torch.from_numpy(v) for k, v in synth.draws(n * 5, Ns, Ni, 0).items()}
+    K = [[F, 0, W / 2], [0, F, H / 2], [0, 0, 1]]
+    outs = (0, 1, 5, 6)
+    names = ("rgb_blur", "rgb0_blur", "rgb", "rgb0")
+
+    def oracle(w, dt, device, rays=n):
+        p = {k: torch.from_numpy(v.copy()).to(device, dt) for k, v in w.items()}
+        with torch.no_grad():
+            o = O.forward_train(p, H, W, F, b["rays"][:rays].to(device, dt), b["images_idx"][:rays].to(device), Ns, Ni, force_naive=False,
+                                allkernel=True, kernel_pixel=b["fq_mask"][:rays].to(device),
+                                draws={k: v[:rays * 5].to(device, dt) for k, v in d.items()})
+        return [o[i].double().cpu() for i in outs]
+
+    w = synth.all_weights(n_img, 0, rbk_scale=2.0e4)
+    g32, g64 = oracle(w, torch.float32, dev), oracle(w, torch.float64, dev)
+    c32, c64 = oracle(w, torch.float32, "cpu", m), oracle(w, torch.float64, "cpu", m)
+    _FULL_SIZE["check"] = {"gpu": max(util.relerr(a[:m], r[:m]) for a, r in zip(g32, g64)),
+                           "cpu": max(util.relerr(a, r) for a, r in zip(c32, c64))}
+    _FULL_SIZE["err"], _FULL_SIZE["beyond"], _FULL_SIZE["f64"] = {}, {}, {}
+    for tl, label in ((True, "trained_like"), ((6000.0, 40.0), "x6000")):
+        w = synth.all_weights(n_img, 0, rbk_scale=2.0e4, trained_like=tl)
+        ref = oracle(w, torch.float32, dev)
+        r64 = oracle(w, torch.float64, dev)
+        _FULL_SIZE["f64"][label, "fp32 oracle"] = max(util.relerr(a, r) for a, r in zip(ref, r64))
+        for name, prec in (("h,h", ops.Precision(ops.PLANES_F16, ops.PLANES_F16)), ("2,2", ops.Precision(2, 2))):
+            net = M.NeRFAll(args, M.RBK(n_img, 64, 4, 64, 1, 32, 1, 32, 1, 32, 3, 3, [4], True, 0.1, 4), precision=prec)
+            M.load_reference_weights(net, w)
+            net = net.to(dev).train()
+            with torch.no_grad():
+                out = net(H, W, K, chunk=1 << 20, rays=b["rays"].to(dev), rays_info={"images_idx": b["images_idx"].to(dev)}, retraw=True,
+                          force_naive=False, allkernel=True, kernel_pixel=b["fq_mask"].to(dev), perturb=1., N_importance=Ni, N_samples=Ns,
+                          use_viewdirs=True, white_bkgd=False, raw_noise_std=1., inference=False, near=0., far=1.,
+                          draws={k: v.to(dev) for k, v in d.items()})
+            assert net.read_faults() == 0
+            err, beyond = {}, {}
+            for oname, i, r in zip(names, outs, ref):
+                per_ray = (out[i].double().cpu() - r).abs().amax(-1) / r.abs().max()
+                err[oname], beyond[oname] = float(per_ray.max()), int((per_ray > 1e-4).sum())
+            _FULL_SIZE["err"][label, name], _FULL_SIZE["beyond"][label, name] = err, beyond
+            _FULL_SIZE["f64"][label, name] = max(util.relerr(out[i].double().cpu(), r) for i, r in zip(outs, r64))
+            print(f"full size, {label}, {name}: " + ", ".join(f"{k} max {err[k]:.2e} ({beyond[k]} of {n} rays beyond 1e-4)" for k in names)
+                  + f"; from float64 {_FULL_SIZE['f64'][label, name]:.2e} (the fp32 oracle: {_FULL_SIZE['f64'][label, 'fp32 oracle']:.2e})", flush=True)
+            del net, out
+    print(f"full size: GPU fp32 oracle from GPU float64 {_FULL_SIZE['check']['gpu']:.2e}, CPU fp32 from CPU float64 "
+          f"{_FULL_SIZE['check']['cpu']:.2e} (initialisation, {m} rays)", flush=True)
+    return _FULL_SIZE
+
+
+@pytest.mark.parametrize("field", [
+    pytest.param("trained_like", marks=pytest.mark.xfail(strict=True, reason=(
+        "(h,h) at 4096 rays on bench.py's trained_like field: rgb 1.03e-4 of the fp32 oracle, 1 of 4096 rays beyond 1e-4 (rgb_blur 9.3e-5); "
+        "the strict (2,2) mode is at 9.97e-5 on the same field")), id="trained_like"),
+    pytest.param("x6000", marks=pytest.mark.xfail(strict=True, reason=(
+        "(h,h) at 4096 rays on the x6000 field: rgb 1.06e-4 of the fp32 oracle, 2 of 4096 rays beyond 1e-4 (rgb_blur 9.6e-5); "
+        "(2,2) 6.3e-5")), id="x6000")])
+def test_headline_output_bound_at_the_bench_size(diag, field):
+    """The north star's 1e-4 for (h,h) on the two sharp fields at N_rand 4096 (_full_size_outputs): known to fail on isolated rays.
+    What holds instead (max < 2.5e-4, at most 4 rays beyond 1e-4) is asserted in test_outputs_stay_inside_the_bound_on_a_trained_like_field."""
+    e = _full_size_outputs()["err"][field, "h,h"]
+    assert max(e.values()) < 1e-4, e
 
 
 @pytest.mark.parametrize("planes", ["2,1", "2,h", "h,h"])
@@ -1476,3 +1581,78 @@ def test_long_training_trajectory_follows_the_reference(diag, planes):
         devs.append(float(dev_w.max()))
     assert np.mean(cosines) > 0.94, cosines
     assert np.mean(devs) < 0.35, devs
+
+
+# Runs per mode of the trained-like trajectory test; its gates, and the spreads they were built on: tests/util.TL_TRAJ_GATES.
+TL_TRAJ_REPS = {"2,2": 4, "2,h": 4, "h,h": 4}          # 0.2 s a run
+
+
+def _trained_like_trajectory(diag, planes):
+    """One run of Trainer.step in `planes` over the fixture's steps (its targets, the same rays and draws): the spread against the
+    fixture's fp32 reference (tests/util.trajectory_spread), the step-0 deviation, the final parameter norms' largest relative miss,
+    and the fault word."""
+    import argparse
+    import numpy as np
+    from lush_nerf_amd import model as M, ops, synth
+    from lush_nerf_amd.trainer import Trainer
+    g = diag.util.golden("train_trajectory_trained_like")
+    n, Ns, Ni, seed, steps = (int(x) for x in g["meta"])
+    dev = torch.device("cuda:0")
+    args = argparse.Namespace(blur_model_type="dpnerf", multires=10, multires_views=4, i_embed=0, use_viewdirs=True,
+                              N_importance=Ni, netdepth=8, netwidth=256, netdepth_fine=8, netwidth_fine=256,
+                              rgb_activate="sigmoid", sigma_activate="relu", tone_mapping_type="gamma", render_rmnearplane=80)
+    w0 = synth.all_weights(30, seed, rbk_scale=2.0e4, trained_like=True)
+    net = M.NeRFAll(args, M.RBK(30, 64, 4, 64, 1, 32, 1, 32, 1, 32, 3, 3, [4], True, 0.1, 4),
+                    precision=ops.Precision(*ops.parse_planes(planes)))
+    M.load_reference_weights(net, w0)
+    net = net.to(dev)
+    tr = Trainer(net, synth.H_DEF, synth.W_DEF, synth.FOCAL_DEF, Ns, Ni, kernel_start_iter=0, allkernel_start_iter=0)
+    targets = torch.from_numpy(g["targets"]).to(dev)
+    losses = []
+    for s in range(steps):
+        b = {k: torch.from_numpy(v).to(dev) for k, v in synth.ray_batch(n, seed, 30, step=s).items()}
+        b["target"] = targets[s]
+        d = {k: torch.from_numpy(v).to(dev) for k, v in synth.draws(n * 5, Ns, Ni, seed, step=s).items()}
+        losses.append(tr.step(b, s, draws=d))
+    losses = np.asarray([float(x) for x in losses])
+    sd = dict(_canon(net))
+    sd.update(net.state_dict())                      # the fixture lists some aliases under their raw names
+    rbk = sorted(k[4:] for k in g if k.startswith("rbk."))
+    final = {k: sd[k] for k in rbk + ["mlp_fine.rgb_linear.weight"]}
+    ref_final = {k: g["rbk." + k] for k in rbk}
+    ref_final["mlp_fine.rgb_linear.weight"] = g["final_rgb_w"]
+    m = diag.util.trajectory_spread(losses, final, g["losses"], ref_final, w0)
+    keys = [str(k) for k in g["final_keys"]]
+    norms = np.array([float(sd[k].double().norm()) for k in keys])
+    m["norms"] = float((np.abs(norms - g["final_norms"]) / np.maximum(g["final_norms"], 1e-12)).max())
+    m["step0"] = float(abs(losses[0] - g["losses"][0]) / g["losses"][0])
+    m["faults"] = int(tr.faults())
+    m["min_cos_rbk"] = min(v for k, v in m["cos"].items() if k.startswith("mlp_rbk."))
+    m["worst_rbk"] = min((v, k) for k, v in m["cos"].items() if k.startswith("mlp_rbk."))[1]
+    m["cos_rgb"] = m["cos"]["mlp_fine.rgb_linear.weight"]
+    print(f"trained-like trajectory {planes}: loss {g['losses'][0]:.3e} -> {g['losses'][-1]:.3e} (reference), {losses[0]:.3e} -> "
+          f"{losses[-1]:.3e} here; per-step deviation max {m['step_dev']:.2e}, windowed {m['win_dev']:.2e}, fall ratio "
+          f"{m['fall_ratio']:.4f}; update cosines: RBK min {m['min_cos_rbk']:.4f} ({m['worst_rbk']}), fine rgb head "
+          f"{m['cos_rgb']:.4f}; final norms within {m['norms']:.2e}; step 0 {m['step0']:.1e}", flush=True)
+    return m
+
+
+@pytest.mark.parametrize("planes", ["2,2", "2,h", "h,h"])
+def test_trained_like_trajectory_follows_the_reference(diag, planes):
+    """60 optimisation steps of the REAL reference from the density field bench.py's `trained_like` workload starts from
+    (make_golden.case_trajectory_trained_like: sharp surfaces behind a x3000 density head, teacher targets, blur kernel on), where
+    d(rays) -- the only way the blur-kernel network learns -- is a cancelling sum, against Trainer.step in the fp32-equivalent
+    mode, the accurate-gradient mode (2,h) and the bench headline (h,h), TL_TRAJ_REPS[mode] runs each: every run inside the
+    gates tests/util.TL_TRAJ_GATES on the loss curve, the loss's fall, the direction of every RBK tensor's and of the fine rgb head's update
+    and the final parameter norms."""
+    G = diag.util.TL_TRAJ_GATES
+    for rep in range(TL_TRAJ_REPS[planes]):
+        m = _trained_like_trajectory(diag, planes)
+        assert m["faults"] == 0
+        assert m["step0"] < 1e-4                                   # step 0 is a pure forward: the 1e-4 output bound
+        assert m["step_dev"] < G["step_dev"], (planes, rep, m["step_dev"])
+        assert m["win_dev"] < G["win_dev"], (planes, rep, m["win_dev"])
+        assert abs(m["fall_ratio"] - 1.0) < G["fall"], (planes, rep, m["fall_ratio"])
+        assert 1.0 - m["min_cos_rbk"] < G["rbk_cos"], (planes, rep, m["worst_rbk"], m["min_cos_rbk"])
+        assert 1.0 - m["cos_rgb"] < G["rgb_cos"], (planes, rep, m["cos_rgb"])
+        assert m["norms"] < G["norms"], (planes, rep, m["norms"])

@@ -314,3 +314,68 @@ def test_trained_like_field_has_empty_space_and_surfaces():
     assert 0.35 < shares["init"][0] < 0.6 and shares["init"][1] == 0.0, shares              # sigma ~ 0: the noise alone decides
     live, above, below = shares["trained_like"]
     assert 0.15 < live < 0.45 and above > 0.12 and below > 0.5, shares                      # surfaces, and mostly empty space
+
+
+def _trained_like_floor(g):
+    """The fixture's fp32 reference run against its float64 run (tests/util.trajectory_spread): the chaos floor of the regime."""
+    w0 = synth.all_weights(util.NUM_IMG, int(g["meta"][3]), rbk_scale=2.0e4, trained_like=True)
+    rbk = sorted(k[4:] for k in g if k.startswith("rbk."))
+    fin = {k: g["rbk." + k] for k in rbk}
+    ref = {k: g["f64." + k] for k in rbk}
+    fin["mlp_fine.rgb_linear.weight"], ref["mlp_fine.rgb_linear.weight"] = g["final_rgb_w"], g["final_rgb_w_f64"]
+    m = util.trajectory_spread(g["losses"], fin, g["losses_f64"], ref, w0)
+    m["norms"] = float((np.abs(g["final_norms"] - g["final_norms_f64"]) / g["final_norms_f64"]).max())
+    return m, w0, rbk
+
+
+# Steps 0-4 of the trained-like trajectory, the oracle against the reference (both fp32, op orders differ): measured 0 at step 0, at most
+# 1.0e-5 (step 3) -- as far as the stored float64 run is from the reference over the same steps (2.4e-5 by step 4): the run is chaotic
+# from its first updates.  Rule: 10 x the largest deviation measured.
+TL_ORACLE_TOL = 1e-4
+
+
+def test_oracle_follows_the_trained_like_trajectory_fixture():
+    """The first steps of make_golden.case_trajectory_trained_like (the reference trained from the trained-like density field on teacher
+    targets) with the fp32 oracle and torch Adam: its losses match the reference's.  And the float64 run stored beside it -- the
+    yardstick of the GPU test's gates -- starts at the same loss: the same computation, in another precision."""
+    g = util.golden("train_trajectory_trained_like")
+    n, Ns, Ni, seed, steps = (int(x) for x in g["meta"])
+    p = util.params(seed, rbk_scale=2.0e4, requires_grad=True, trained_like=True)
+    opt = torch.optim.Adam(list(p.values()), lr=5e-4)
+    losses = []
+    for s in range(5):
+        b = synth.ray_batch(n, seed, util.NUM_IMG, step=s)
+        d = {k: torch.from_numpy(v) for k, v in synth.draws(n * 5, Ns, Ni, seed, step=s).items()}
+        out = O.forward_train(p, util.H, util.W, util.FOCAL, torch.from_numpy(b["rays"]), torch.from_numpy(b["images_idx"]), Ns, Ni,
+                              force_naive=False, allkernel=False, kernel_pixel=torch.from_numpy(b["fq_mask"]), draws=d)
+        loss = O.train_loss(out[0], out[1], torch.from_numpy(g["targets"][s]))
+        opt.zero_grad()
+        loss.backward()
+        opt.step()
+        for grp in opt.param_groups:
+            grp["lr"] = O.lr_at(s)
+        losses.append(loss.item())
+    dev = np.abs(np.asarray(losses) - g["losses"][:5]) / g["losses"][:5]
+    print("oracle against the trained-like trajectory fixture, steps 0-4:", dev)
+    assert dev[0] < 1e-6                    # step 0 is a forward: the oracle and the reference differ by rounding only
+    assert dev.max() < TL_ORACLE_TOL, dev
+    assert abs(g["losses_f64"][0] - g["losses"][0]) / g["losses"][0] < 1e-5
+
+
+def test_trained_like_trajectory_fixture_floor():
+    """The fixture is a run that trains, and the GPU test's gates (tests/util.TL_TRAJ_GATES) sit at least 2 x above the chaos floor it
+    stores (the reference's fp32 run against float64 of the same computation): a GPU run is never asked to follow the reference more
+    closely than float64 does."""
+    g = util.golden("train_trajectory_trained_like")
+    m, w0, rbk = _trained_like_floor(g)
+    G = util.TL_TRAJ_GATES
+    min_cos = min(m["cos"][k] for k in rbk)
+    print("trained-like trajectory floor (fp32 reference against float64):", {k: v for k, v in m.items() if k != "cos"},
+          "RBK update cosine min", min_cos, "fine rgb head", m["cos"]["mlp_fine.rgb_linear.weight"])
+    for r in (g["losses"], g["losses_f64"]):
+        assert r[-10:].mean() < r[:10].mean() / 5                  # the loss falls: 9.9e-3 -> ~6e-4
+    for k in rbk:                                                  # every RBK tensor moves measurably
+        assert np.linalg.norm(g["rbk." + k] - w0[k]) > 1e-3 * max(np.linalg.norm(w0[k]), 1.0), k
+    assert 2 * m["step_dev"] <= G["step_dev"] and 2 * m["win_dev"] <= G["win_dev"] and 2 * abs(m["fall_ratio"] - 1) <= G["fall"]
+    assert 2 * (1 - min_cos) <= G["rbk_cos"] and 2 * (1 - m["cos"]["mlp_fine.rgb_linear.weight"]) <= G["rgb_cos"]
+    assert 2 * m["norms"] <= G["norms"]

@@ -152,3 +152,41 @@ class masked_oracle:
 
     def __exit__(self, *a):
         self.O.nerf_mlp = self.orig
+
+
+TL_TRAJ_WIN = 10
+# Gates of tests/test_gpu_parity.py::test_trained_like_trajectory_follows_the_reference (60 steps from the trained-like density field on
+# teacher targets, tests/golden/train_trajectory_trained_like.npz), one set for every mode, each ~2 x the larger of two measured spreads
+# (trajectory_spread), never a mode's own figure:
+#   floor  = the reference's fp32 run against the float64 run of the same computation, stored in the fixture
+#            (tests/test_oracle_golden.py::test_trained_like_trajectory_fixture_floor checks every gate is >= 2 x it);
+#   (2,2)  = 6 runs of the fp32-equivalent mode against the fp32 reference (worst run), which differ from one another only in the order
+#            of the fp32 atomics of the weight-gradient sums.
+#                                                    floor     (2,2), worst of 6
+#   per-step relative loss deviation, max            0.233     0.169
+#   windowed (10-step means) deviation, max          0.112     0.066
+#   |loss fall / reference's fall - 1|               0.017     0.0087
+#   1 - cos, update of the worst mlp_rbk.* tensor    0.048     0.077   (view_embed_linears.0.bias / .1.weight)
+#   1 - cos, update of the fine rgb head             0.0042    0.0023
+#   final parameter norms, largest relative miss     2.3e-3    4.2e-3
+# Measured after the gates were set, worst of 4 runs each: (2,h) 0.287 / 0.095 / 0.012 / 0.084 / 0.0019 / 5.3e-3; (h,h) 0.316 / 0.145 /
+# 0.019 / 0.145 (RBK update cosine 0.855, r_branch.0.bias: the closest to its gate) / 0.0049 / 4.8e-3.
+TL_TRAJ_GATES = {"step_dev": 0.47, "win_dev": 0.23, "fall": 0.035, "rbk_cos": 0.155, "rgb_cos": 0.0085, "norms": 8.5e-3}
+
+
+def trajectory_spread(losses, final, ref_losses, ref_final, init, win=TL_TRAJ_WIN):
+    """How far one training run lands from another (tests/golden/train_trajectory_trained_like.npz): the largest per-step and
+    windowed (means over `win` steps) relative loss deviation, the ratio of the loss's fall (first window's mean minus the last's)
+    to the other run's, and per tensor of `final` the cosine between its update over the run (final - init) and the other run's.
+    One function for the CPU floor (the reference's fp32 run against its float64 run) and the GPU runs."""
+    l, r = np.asarray(losses, np.float64), np.asarray(ref_losses, np.float64)
+    n = len(r) // win * win
+    mg, mr = l[:n].reshape(-1, win).mean(1), r[:n].reshape(-1, win).mean(1)
+    cos = {}
+    for k, v in final.items():
+        i = np.asarray(init[k], np.float64).ravel()
+        du = np.asarray(v.detach().cpu() if isinstance(v, torch.Tensor) else v, np.float64).ravel() - i
+        dr = np.asarray(ref_final[k], np.float64).ravel() - i
+        cos[k] = float(du @ dr / max(np.linalg.norm(du) * np.linalg.norm(dr), 1e-300))
+    return {"step_dev": float((np.abs(l - r) / r).max()), "win_dev": float((np.abs(mg - mr) / mr).max()),
+            "fall_ratio": float((mg[0] - mg[-1]) / (mr[0] - mr[-1])), "cos": cos}
