@@ -1,7 +1,7 @@
 #!/usr/bin/env python3
 """Training rays/s of the LuSh-NeRF ray-march hot path on MI355X (BASELINE.json metric).
 
-  python bench.py --gpus N --steps K --warmup W
+  python bench.py --gpus N --steps K --warmup W [--full]
   N > 1 either under a launcher (python -m torch.distributed.run --nnodes=1 --nproc-per-node N ... bench.py --gpus N ...)
   or plainly: with WORLD_SIZE unset, bench.py starts the N ranks itself as a child torch.distributed.run
   BEFORE anything touches the GPU, and exits with the child's code.  It refuses to run when the RCCL world
@@ -13,6 +13,11 @@ N_rand = 4096 input rays, N_samples 64 + N_importance 64, blur kernel (RBK/"DSK"
 LLFF-shaped rays resident in HBM before the timed region.  Ranks
 shard rays (weak scaling); the only collective is one RCCL all-reduce of the flat
 gradient buffer.  Rank 0 prints ONE JSON line.
+
+A plain run does what the headline figure needs and nothing else: it sets up, runs W warm-up and K timed steps, writes
+--dump-outputs if asked, and prints the line.  --full adds every other measurement, each behind the headline's timed
+steps: the kernel-group pass (`kernels`, `roofline`, at N = 1 its two rocprofv3 traffic passes), the sustained replay, the
+dense-backward run, the other modes (--also), the other BASELINE configs (--extra) and the CPU baseline.
 """
 import argparse
 import json
@@ -269,30 +274,33 @@ def main():
     ap.add_argument("--n-importance", type=int, default=64)
     ap.add_argument("--planes", type=str, default="h,h", help="16-bit planes per MFMA operand fwd,bwd: h = one fp16 plane (backward: "
                     "loss-scaled), 1..3 = bf16 planes.  Default = the fastest mode that passes every parity gate (tests/test_gpu_parity.py)")
-    ap.add_argument("--also", type=str, default="2,2;2,1;2,h", help="other modes timed after the headline (rank 0 reports them under modes; "
-                    "2,2 = the strict fp32-equivalent mode, printed next to value); empty to skip")
+    ap.add_argument("--full", action="store_true", help="after the headline, measure everything else this script measures (the module "
+                    "docstring lists it); the options marked (--full) choose among those passes.  Without it: the headline figure alone")
+    ap.add_argument("--also", type=str, default=None, help="(--full) other modes timed after the headline (rank 0 reports them under modes; "
+                    "2,2 = the strict fp32-equivalent mode, printed next to value; default 2,2;2,1;2,h); empty to skip")
     ap.add_argument("--micro-batch", type=int, default=0, help="input rays per forward+backward slice (0 = whole batch); "
                     "bounds the activation stash for the larger BASELINE configs")
-    ap.add_argument("--no-cpu-baseline", action="store_true")
+    ap.add_argument("--no-cpu-baseline", action="store_true", help="(--full) skip the CPU baseline")
     ap.add_argument("--variant", type=int, default=0, help="developer A/B: lib.VARIANT_* bits, an older kernel for the same work "
                     "(include/lush_march.h); 0 = the product's choice, the only value a reported line may carry")
-    ap.add_argument("--no-kernel-pass", action="store_true", help="skip the second, kernel-group-timed pass over the steps (profiling "
+    ap.add_argument("--no-kernel-pass", action="store_true", help="(--full) skip the second, kernel-group-timed pass over the steps (profiling "
                     "runs: the process then launches exactly what the timed region launches; the line carries no `kernels` / `roofline`)")
-    ap.add_argument("--no-traffic", action="store_true", help="do not measure roofline.traffic (two child rocprofv3 --pmc passes of this "
-                    "command, rank 0, N = 1 only); quote profiles/pmc_traffic.json instead")
+    ap.add_argument("--no-traffic", action="store_true", help="(--full) do not measure roofline.traffic (two child rocprofv3 --pmc passes of "
+                    "this command, rank 0, N = 1 only); quote profiles/pmc_traffic.json instead")
     ap.add_argument("--so", type=str, default=None, help="developer A/B: another build of the library (tools/build_variant.py); the line "
                     "then carries its path under `library` -- a reported line has none")
-    ap.add_argument("--sustained", type=float, default=3.0, help="seconds of back-to-back headline steps behind the timed region, reported "
-                    "under `sustained` (0 to skip)")
-    ap.add_argument("--no-dense", action="store_true", help="skip the comparison run with the backward over all the points (dense_backward)")
+    ap.add_argument("--sustained", type=float, default=None, help="(--full) seconds of back-to-back headline steps behind the timed region, "
+                    "reported under `sustained` (default 3; 0 to skip)")
+    ap.add_argument("--no-dense", action="store_true", help="(--full) skip the comparison run with the backward over all the points "
+                    "(dense_backward)")
     ap.add_argument("--rehearse-on-one-gpu", action="store_true", help="developer: run the N ranks of --gpus N on the GPUs that exist "
                     "(rank r on device r mod count), collectives over gloo -- a rehearsal of the multi-rank control flow on a one-GPU box; "
                     "the line says so under `rehearsal` and is not a measurement")
-    ap.add_argument("--cpu-n-rand", type=int, default=512, help="input rays of the CPU baseline's kernel-on step (SURVEY 8d: 512)")
+    ap.add_argument("--cpu-n-rand", type=int, default=512, help="(--full) input rays of the CPU baseline's kernel-on step (SURVEY 8d: 512)")
     ap.add_argument("--config", type=str, default="C2", choices=["C2", "C3", "C5"],
                     help="BASELINE config timed as the headline workload (C2 = the one the metric is quoted on)")
-    ap.add_argument("--extra", type=str, default=None, help="other BASELINE configs reported under extra_configs "
-                    "(default at 1 GPU: C1,C3,C5,eval; none on multi-GPU runs); empty to skip")
+    ap.add_argument("--extra", type=str, default=None, help="(--full) other BASELINE configs reported under extra_configs "
+                    "(default at 1 GPU: trained_like,C1,C3,C5,eval; none on multi-GPU runs); empty to skip")
     ap.add_argument("--dump-outputs", type=str, default=None, metavar="DIR", help="after the timed steps, write what the headline's "
                     "last timed step computed (rank 0: `loss`; init_* = the same step from the seeded initial model: its loss, render "
                     "outputs and MLP gradient) as DIR/<name>.npy, float32, so that two builds run with the same arguments can be compared "
@@ -302,6 +310,16 @@ def main():
         raise SystemExit("--gpus must be >= 1")
     if a.steps < 1:
         raise SystemExit("--steps must be >= 1")
+    if a.full:
+        a.also = "2,2;2,1;2,h" if a.also is None else a.also
+        a.sustained = 3.0 if a.sustained is None else a.sustained
+    else:
+        # a plain run: the headline figure and nothing else.  An option that asks for one of --full's passes is refused, not ignored
+        asked = [o for o, v in (("--also", a.also), ("--extra", a.extra), ("--sustained", a.sustained)) if v]
+        if asked:
+            raise SystemExit(f"{', '.join(asked)}: measured in --full runs only (add --full)")
+        a.also, a.extra, a.sustained = "", "", 0.0
+        a.no_cpu_baseline = a.no_kernel_pass = a.no_traffic = a.no_dense = True
     if a.config != "C2":
         c = CONFIGS[a.config]
         a.n_rand, a.n_samples, a.n_importance = c["n_rand"], c["ns"], c["ni"]
@@ -758,10 +776,11 @@ def main():
             # stream, mean over the timed steps): what an N > 1 run adds to the N = 1 step
             "allreduce_ms": round(groups.get("_allreduce_ms", 0.0), 4),
             "sustained": groups.get("_sustained"),
-            "kernel_timing": "HIP events around each MLP kernel group on the launch stream, over the same steps run once more "
-                             "group by group (the timed region makes one lush_march_fwd / lush_march_bwd call per march and has no "
-                             "events inside; every kernel runs alone on the one stream in both passes)",
         }
+        if not a.no_kernel_pass:      # (profiles/summarize.py counts the steps a profiled process ran by this key)
+            out["kernel_timing"] = ("HIP events around each MLP kernel group on the launch stream, over the same steps run once more "
+                                    "group by group (the timed region makes one lush_march_fwd / lush_march_bwd call per march and has no "
+                                    "events inside; every kernel runs alone on the one stream in both passes)")
         notes = {"2,h": "forward 2 bf16 planes, backward ONE loss-scaled fp16 plane (11-bit operands at the bf16 backward's cost)",
                  "h,h": "forward ONE fp16 plane (outputs within 3e-5 of fp32), backward ONE loss-scaled fp16 plane",
                  "2,2": "every MFMA operand in 2 bf16 planes, forward AND backward (fp32-equivalent gradients)",
@@ -796,9 +815,9 @@ def main():
                                                     "dense_ms": out["ms_per_step_dense"],
                                                     "note": "a = the forward over all the points + everything outside the MLPs; the dense backward is the cheaper "
                                                             "one above share = (dense_ms - a) / b (profiles/r05_live_points.md: 5.28 + 14.54 x share over 600 steps)"}
-        if world > 1:      # a SCALE line explains what it leaves out
-            out["n1_only"] = ("cpu_baseline, roofline.traffic (live rocprofv3 --pmc passes) and extra_configs are N = 1 quantities: see the "
-                              "N = 1 line of the same round (BENCH_rNN.json); roofline.traffic here quotes profiles/pmc_traffic.json")
+        if world > 1 and a.full:      # a SCALE line explains what it leaves out
+            out["n1_only"] = ("cpu_baseline, roofline.traffic (live rocprofv3 --pmc passes) and extra_configs are N = 1 quantities: see an "
+                              "N = 1 --full line of the same build; roofline.traffic here quotes profiles/pmc_traffic.json")
         if not a.no_cpu_baseline and world == 1:
             progress(f"CPU baseline (oracle on the host cores, N_rand {a.cpu_n_rand} kernel-on + config 1)")
             out["cpu_baseline"] = cpu_baseline(a.cpu_n_rand, 64, 64, progress=progress)

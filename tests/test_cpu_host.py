@@ -338,6 +338,21 @@ def test_bench_dump_outputs_writes_float_arrays(tmp_path, monkeypatch):
     assert "--gpus must be >= 1" in (r.stderr + r.stdout), r.stderr[-400:]
 
 
+def test_bench_plain_run_refuses_what_only_full_measures():
+    """A plain bench.py run measures the headline alone: an option that asks for one of --full's passes is refused before anything
+    touches a device, not silently dropped; with --full the same options parse (the run then stops at the --gpus check)."""
+    bench = os.path.join(ROOT, "bench.py")
+    for opt in (["--also", "2,2"], ["--extra", "C1"], ["--sustained", "3"]):
+        r = subprocess.run([sys.executable, bench, *opt], capture_output=True, text=True, timeout=300)
+        assert r.returncode != 0 and opt[0] in r.stderr and "--full" in r.stderr and '"metric"' not in r.stdout, r.stderr[-400:]
+    r = subprocess.run([sys.executable, bench, "--full", "--also", "2,2", "--extra", "C1", "--sustained", "3", "--gpus", "0"],
+                       capture_output=True, text=True, timeout=300)
+    assert "--gpus must be >= 1" in (r.stderr + r.stdout), r.stderr[-400:]
+    # asking for none of them is a plain run (the traffic child's own tail: tests above)
+    r = subprocess.run([sys.executable, bench, "--also=", "--extra=", "--sustained", "0", "--gpus", "0"], capture_output=True, text=True, timeout=300)
+    assert "--gpus must be >= 1" in (r.stderr + r.stdout), r.stderr[-400:]
+
+
 def test_trainer_lr_follows_reference_loop():
     """run_lushnerf.py:675-685, 788: step g runs with the rate computed from global_step g-1."""
     from oracle import lush_oracle as O

@@ -783,17 +783,17 @@ def test_bench_two_ranks_rehearsal(diag, tmp_path, ranks):
     """bench.py's multi-rank control flow with real kernels on the box we have: `--gpus 2` (and 4: the driver's scaling run goes 1, 2,
     4, 8) starts the ranks itself; with
     `--rehearse-on-one-gpu` both use the one card and the collectives go over gloo.  What it pins: no rank-dependent loop count
-    in front of a collective (every step of every pass holds one: warm-up, timed region, kernel-group pass, sustained cycles,
-    the dense-backward comparison, the other modes), ONE JSON line from rank 0 with n_gpus = 2 and the whole-job value, the
-    `n1_only` and `rehearsal` notes.  Not a measurement."""
+    in front of a collective (every step of every pass holds one: warm-up, timed region, and with --full the kernel-group pass,
+    sustained cycles, the dense-backward comparison, the other modes), ONE JSON line from rank 0 with n_gpus = 2 and the whole-job
+    value, the `n1_only` and `rehearsal` notes.  Not a measurement."""
     import json, os, subprocess, sys
     root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
     env = dict(os.environ, HSA_ENABLE_IPC_MODE_LEGACY="0")
     for k in ("RANK", "LOCAL_RANK", "WORLD_SIZE", "MASTER_PORT"):
         env.pop(k, None)
     r = subprocess.run([sys.executable, os.path.join(root, "bench.py"), "--gpus", str(ranks), "--rehearse-on-one-gpu", "--steps", "3", "--warmup", "2",
-                        "--n-rand", "1024", "--no-cpu-baseline", "--also=2,2" if ranks == 2 else "--also=", "--sustained", "0.3"], capture_output=True, text=True,
-                       timeout=420, env=env, cwd=str(tmp_path))
+                        "--n-rand", "1024", "--full", "--no-cpu-baseline", "--also=2,2" if ranks == 2 else "--also=", "--sustained", "0.3"],
+                       capture_output=True, text=True, timeout=420, env=env, cwd=str(tmp_path))
     assert r.returncode == 0, r.stdout[-1500:] + r.stderr[-3000:]
     lines = [l for l in r.stdout.splitlines() if l.startswith("{")]
     assert len(lines) == 1, r.stdout[-2000:]
@@ -838,6 +838,28 @@ def test_bench_dump_outputs(diag, tmp_path):
         assert v.shape == ((1,) if k.endswith("loss") else (n_mlp,) if k == "init_grad_mlp" else (256, 3)), (k, v.shape)
     assert float(np.abs(arr["init_grad_mlp"]).max()) > 0 and float(np.abs(arr["init_rgb"]).max()) > 0
     assert arr["loss"][0] != arr["init_loss"][0]
+
+
+def test_bench_plain_run_times_the_headline_only(diag, tmp_path):
+    """bench.py without --full: set-up, warm-up, the timed steps and the line -- the headline's keys, and nothing that one of --full's
+    passes measures (kernel groups and roofline, sustained replay, dense backward, other modes and configs, CPU baseline)."""
+    import json, os, subprocess, sys
+    root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+    env = dict(os.environ)
+    for k in ("RANK", "LOCAL_RANK", "WORLD_SIZE", "MASTER_PORT"):
+        env.pop(k, None)
+    r = subprocess.run([sys.executable, os.path.join(root, "bench.py"), "--gpus", "1", "--steps", "2", "--warmup", "1", "--n-rand", "256"],
+                       capture_output=True, text=True, timeout=300, env=env, cwd=str(tmp_path))
+    assert r.returncode == 0, r.stdout[-1500:] + r.stderr[-3000:]
+    lines = [l for l in r.stdout.splitlines() if l.startswith("{")]
+    assert len(lines) == 1, r.stdout[-2000:]
+    d = json.loads(lines[0])
+    assert d["metric"] == "training rays/sec (fwd+bwd), N_samples=64+64" and d["unit"] == "rays/s" and d["higher_is_better"] is True
+    assert d["steps"] == 2 and d["warmup"] == 1 and d["ms_per_step"] > 0 and d["value"] == pytest.approx(256 / (d["ms_per_step"] * 1e-3), rel=1e-2)
+    assert d["dtype"].startswith("f16 MFMA forward") and d["live_points"]["share"] > 0.2
+    assert d["kernels"] == {} and d["roofline"] is None and d["sustained"] is None and d["dense_backward"] is None
+    assert not {"modes", "extra_configs", "cpu_baseline", "kernel_timing", "n1_only"} & set(d), sorted(d)
+    assert "dense backward" not in r.stderr and "extra config" not in r.stderr and "CPU baseline" not in r.stderr, r.stderr[-2000:]
 
 
 @pytest.mark.parametrize("kernel_on", [True, False])

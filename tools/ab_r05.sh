@@ -14,7 +14,7 @@ for rep in 1 2; do
   done
 done
 for v in 0 17 0 17; do
-  python bench.py --steps 2 --warmup 1 --no-cpu-baseline --no-traffic --no-kernel-pass --sustained 0 --also "" --extra C1 --variant $v 2>/dev/null | python -c "
+  python bench.py --steps 2 --warmup 1 --full --no-cpu-baseline --no-traffic --no-kernel-pass --sustained 0 --also "" --extra C1 --variant $v 2>/dev/null | python -c "
 import json,sys
 d=json.loads(sys.stdin.read().strip().splitlines()[-1]); print('C1 variant', $v, d['extra_configs']['C1']['ms_per_step'], d['extra_configs']['C1'].get('ms_per_step_eager'))"
 done

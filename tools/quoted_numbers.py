@@ -104,7 +104,7 @@ def blocks():
         cb = u.get("cpu_baseline") or {}
         if cb:
             rows.append(f"| CPU oracle on the box's {cb.get('cores')} host threads (N_rand 512, kernel on) | {cb.get('value', 0):.1f} | {cb.get('s_per_step', 0) * 1e3:,.0f} | `cpu_baseline` (kind: port); GPU / CPU = {u.get('gpu_over_cpu', 0):,.0f} |")
-        rows.append(f"\n(`profiles/{tag}_bench_unprofiled.json`: one `python bench.py --steps 20 --warmup 5` on one box; boxes differ by 2 - 4 %.)")
+        rows.append(f"\n(`profiles/{tag}_bench_unprofiled.json`: one `python bench.py --steps 20 --warmup 5 --full` on one box; boxes differ by 2 - 4 %.)")
         out["configs"] = "\n".join(rows)
     # ---- kernel table
     if line:

@@ -1,7 +1,7 @@
 #!/usr/bin/env python3
-"""Developer tool: the launches of one replayed BASELINE-config-1 step (bench.py --extra C1) from a rocprofv3 kernel trace.
-  rocprofv3 --kernel-trace --output-format csv -d gpurun_out/trace_c1 -- python3 bench.py --steps 1 --warmup 1 --no-cpu-baseline --also "" --extra C1
-  python tools/trace_c1.py gpurun_out/trace_c1"""
+"""Developer tool: the launches of one replayed BASELINE-config-1 step (bench.py --full --extra C1) from a rocprofv3 kernel trace.
+  rocprofv3 --kernel-trace --output-format csv -d trace_c1 -- python3 bench.py --steps 1 --warmup 1 --full --no-cpu-baseline --also "" --extra C1
+  python tools/trace_c1.py trace_c1"""
 import csv, glob, os, sys
 src = sys.argv[1]
 f = sorted(glob.glob(os.path.join(src, "**", "*kernel_trace.csv"), recursive=True), key=os.path.getmtime)[-1]
