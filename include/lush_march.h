@@ -279,6 +279,9 @@ typedef struct {
                                       * all the jobs of its slice of the points */
 #define LUSH_VARIANT_DENSE_BWD 256   /* lush_march_fwd / _bwd in the headline mode: stash every point in the forward and run the backward over all of them
                                       * (rounds 1-4) instead of re-running the forward and the backward on the live points only (round 5) */
+#define LUSH_VARIANT_DW_WALK 512     /* weight gradients of a large pass: every workgroup walks all the jobs of its 1/256 of the points (rounds 1-6: ten
+                                      * drains / flushes / refills per workgroup) instead of claiming chunks of one job at a time from per-job
+                                      * cursors (round 7: DESIGN.md section 5).  An older-kernel bit: a march given it runs the dense form */
 #define LUSH_VARIANT_KERNEL_BITS 0x3DF /* every bit above that selects a kernel; anything else in the word is ignored */
 
 size_t lush_mlp_packed_bytes(int net, int planes);

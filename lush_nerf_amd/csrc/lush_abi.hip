@@ -52,7 +52,7 @@ DStashLayout dstash_layout(const NetInfo& n, int ns, long long P) {
     DStashLayout L{};
     const long long Ppad = pad_pts(P);
     size_t off = 0;
-    L.scale = off; off += 256;      // {loss scale, 1/scale, 2 work words} of the fp16 gradient chain
+    L.scale = off; off += 256;      // {loss scale, 1/scale, 2 work words} of the fp16 gradient chain, then DW_MAX_JOBS chunk cursors (DwGroup::cursor)
     // 1 and 2 planes: fp32 scratch G = dZv^T h_{NL-1} [HV][HW] then s = sum dZv [HV] (FeatFactorArgs), no d_feature array
     // (one plane: DZV_EXT more rows of G / s for the heads, and the [DZV_EXT][HV] + [DZV_EXT] block of the rgb job)
     L.fac = off; off += ns <= 2 ? al256((size_t)((n.HV + DZV_EXT) * (n.HW + 1) + DZV_EXT * (n.HV + 1)) * 4) : 0;
@@ -416,7 +416,7 @@ int lush_debug_stash_layout(int net, int planes, long long P, long long* o) {
 // 128-point-tile chain kernels of the bf16-plane modes, with the grouped weight gradients), no older-kernel variant bit; the
 // three-plane reference mode keeps its tiled kernels and the backward over all the points
 static const int LIVE_OLDER_VARIANTS = LUSH_VARIANT_FWD_HALF | LUSH_VARIANT_FWD_512 | LUSH_VARIANT_BWD_HALF | LUSH_VARIANT_BWD_512 | LUSH_VARIANT_PE_ROWS |
-                                       LUSH_VARIANT_HEAD_KERNEL | LUSH_VARIANT_DW_SPLIT;
+                                       LUSH_VARIANT_HEAD_KERNEL | LUSH_VARIANT_DW_SPLIT | LUSH_VARIANT_DW_WALK;
 static bool live_kernels(int net, int planes_f, int planes_b, int variant) {
     return net == 0 && mlp_fwd_chain_enabled(planes_f) && mlp_bwd_chain_enabled(planes_b) && !(variant & LIVE_OLDER_VARIANTS);
 }
@@ -529,8 +529,9 @@ static int mlp_bwd_impl(int net, int planes_f, int planes_b, const float* rays, 
         // (chain and weight gradients in ONE call -- the noise net's backward: the loss-scale launch also zeroes the scratch the
         // grouped launch accumulates into, instead of a fill launch of its own)
         fac_zeroed = do_weights && planes_b <= 2;
-        rc = launch_grad_scale(draw, P * 4, gscale, fac_zeroed ? (float*)(db + D.fac) : nullptr,
-                               fac_zeroed ? (long long)((n.HV + DZV_EXT) * (n.HW + 1) + DZV_EXT * (n.HV + 1)) : 0, st);
+        // (with the chunk queue's cursors in front of it: the header's bytes behind the scale and the work words)
+        rc = launch_grad_scale(draw, P * 4, gscale, fac_zeroed ? (float*)(db + D.scale + DW_CURSOR_OFF) : nullptr,
+                               fac_zeroed ? (long long)((D.fac - D.scale - DW_CURSOR_OFF) / 4 + (n.HV + DZV_EXT) * (n.HW + 1) + DZV_EXT * (n.HV + 1)) : 0, st);
         if (rc) return rc;
     }
     if (do_chain) rc = chain ? launch_mlp_chain_bwd(net, code_b, a, variant, st) : launch_mlp_bwd(net, planes_b, a, grid, st);
@@ -610,7 +611,8 @@ static int mlp_bwd_impl(int net, int planes_f, int planes_b, const float* rays, 
         float* facS = facG + (size_t)grow * n.HW;            // [grow]
         float* facH = facS + grow;                           // [DZV_EXT][HV]
         float* facSH = facH + (size_t)DZV_EXT * n.HV;        // [DZV_EXT]
-        if (!prepared && !fac_zeroed) LUSH_HIP(hipMemsetAsync(facG, 0, (size_t)(grow * (n.HW + 1) + DZV_EXT * (n.HV + 1)) * 4, st));
+        if (!prepared && !fac_zeroed)      // (and the chunk queue's cursors in front of it)
+            LUSH_HIP(hipMemsetAsync(db + D.scale + DW_CURSOR_OFF, 0, (D.fac - D.scale - DW_CURSOR_OFF) + (size_t)(grow * (n.HW + 1) + DZV_EXT * (n.HV + 1)) * 4, st));
         {
             DwJob& j = job(a.dzv, ldzv, fold && alpha ? grow : n.HV, H(n.NL - 1), n.HW, 0, n.HW, facG, n.HW, 0, facS);
             with_pe(j, PE_X, DV, g->w_views, n.HW + DV, n.HW);
@@ -624,6 +626,40 @@ static int mlp_bwd_impl(int net, int planes_f, int planes_b, const float* rays, 
         // 4 096 points 0.107 -> 0.064 ms).  Above it a job's streaming time hides its atomics and every workgroup takes every job of
         // its slice in turn, which balances the narrow jobs.
         // (LUSH_DW_PERJOB_MAX_PTS / _MIN_PTS: lush_mlp.h; a live-point launch makes the same choice on the device)
+        // cus workgroups shared out over the jobs in proportion to what a point of each job costs a workgroup (the comment at
+        // LUSH_VARIANT_DW_SPLIT below); every job gets at least one
+#ifndef LUSH_DW_PE_COST
+#define LUSH_DW_PE_COST 860
+#endif
+        auto job_shares = [&](int cus, int* nj) {
+            long long w[DW_MAX_JOBS], W = 0;
+            for (int i = 0; i < G.n; ++i) {
+                const DwJob& j = G.j[i];
+                const bool pe = j.X2 != nullptr && G.xd != nullptr && j.pe_mode != 0;
+                w[i] = 2LL * (j.n_out + j.k_in) + (j.X2 && !pe ? 2LL * j.k2_in : 0);
+                if (w[i] < 512) w[i] = 512;
+                if (pe) w[i] += 32 + LUSH_DW_PE_COST;
+                W += w[i];
+            }
+            int used = 0;
+            double frac[DW_MAX_JOBS];
+            for (int i = 0; i < G.n; ++i) {
+                const double x = (double)cus * (double)w[i] / (double)W;
+                nj[i] = (int)x < 1 ? 1 : (int)x;
+                frac[i] = x - (int)x;
+                used += nj[i];
+            }
+            while (used < cus) {                       // the CUs left over go to the jobs that were rounded down the most
+                int b = 0;
+                for (int i = 1; i < G.n; ++i) if (frac[i] > frac[b]) b = i;
+                ++nj[b]; frac[b] = -1.0; ++used;
+            }
+            while (used > cus) {                       // (only when a narrow job was lifted to one workgroup)
+                int b = 0;
+                for (int i = 1; i < G.n; ++i) if (nj[i] > nj[b]) b = i;
+                --nj[b]; --used;
+            }
+        };
         int splits = dw_splits(L.Ppad);
         G.per_job = 0;
         G.live_cnt = live_cnt;
@@ -652,36 +688,8 @@ static int mlp_bwd_impl(int net, int planes_f, int planes_b, const float* rays, 
             // split, -DLUSH_CLOCK): the bytes the job streams (Z row + X row), at least 512 (a narrow job is latency-bound: three
             // small stages in flight), plus DW_PE_COST for a block that is re-encoded from the 32-byte point record (the
             // encoding's ~150 VALU instructions per stage run on four of the eight waves: 27 ns per point).
-#ifndef LUSH_DW_PE_COST
-#define LUSH_DW_PE_COST 860
-#endif
-            long long w[DW_MAX_JOBS], W = 0;
-            for (int i = 0; i < G.n; ++i) {
-                const DwJob& j = G.j[i];
-                const bool pe = j.X2 != nullptr && G.xd != nullptr && j.pe_mode != 0;
-                w[i] = 2LL * (j.n_out + j.k_in) + (j.X2 && !pe ? 2LL * j.k2_in : 0);
-                if (w[i] < 512) w[i] = 512;
-                if (pe) w[i] += 32 + LUSH_DW_PE_COST;
-                W += w[i];
-            }
-            int nj[DW_MAX_JOBS], used = 0;
-            double frac[DW_MAX_JOBS];
-            for (int i = 0; i < G.n; ++i) {
-                const double x = (double)cus * (double)w[i] / (double)W;
-                nj[i] = (int)x < 1 ? 1 : (int)x;
-                frac[i] = x - (int)x;
-                used += nj[i];
-            }
-            while (used < cus) {                       // the CUs left over go to the jobs that were rounded down the most
-                int b = 0;
-                for (int i = 1; i < G.n; ++i) if (frac[i] > frac[b]) b = i;
-                ++nj[b]; frac[b] = -1.0; ++used;
-            }
-            while (used > cus) {                       // (only when a narrow job was lifted to one workgroup)
-                int b = 0;
-                for (int i = 1; i < G.n; ++i) if (nj[i] > nj[b]) b = i;
-                --nj[b]; --used;
-            }
+            int nj[DW_MAX_JOBS];
+            job_shares(cus, nj);
             grid_x = 0;
             for (int i = 0; i < G.n; ++i) {
                 long long p = (L.Ppad + nj[i] - 1) / nj[i];
@@ -692,6 +700,19 @@ static int mlp_bwd_impl(int net, int planes_f, int planes_b, const float* rays, 
             }
             G.first[G.n] = grid_x;
             G.per_job = 2;
+        }
+        if (!G.per_job && L.Ppad > LUSH_DW_PERJOB_MAX_PTS && !(variant & LUSH_VARIANT_DW_WALK) && grid_x >= 2 * G.n) {
+            // The product's choice above LUSH_DW_PERJOB_MAX_PTS points, dense and live (a live launch whose list turns out shorter
+            // falls back to one job per workgroup in the kernel, as before): the chunk queue (DwGroup::per_job == 3).  The walk paid
+            // ten drain / flush / zero / refill boundaries per workgroup whatever the point count (profiles/r07_dw_queue.md);
+            // here a workgroup flushes when the job it streams runs out of chunks.  The cursors are zero: they lie in the dstash
+            // header, which is zeroed together with the feature-factor scratch behind it.
+            int nj[DW_MAX_JOBS];
+            job_shares(grid_x, nj);
+            G.first[0] = 0;
+            for (int i = 0; i < G.n; ++i) G.first[i + 1] = G.first[i] + nj[i];
+            G.cursor = (int*)(db + D.scale + DW_CURSOR_OFF);
+            G.per_job = 3;
         }
         rc = launch_dw_group(G, grid_x, planes_b, x_f16, z_f16, st);
         if (rc) return rc;
@@ -788,8 +809,9 @@ bool mlp_dstash_header(int net, int planes_b, long long P, void* dstash, float**
     char* db = (char*)dstash;
     *scale4 = planes_b == PLANES_F16 ? (float*)(db + D.scale) : nullptr;
     const bool fac = ns <= 2;
-    *zero_buf = fac ? (float*)(db + D.fac) : nullptr;
-    *zero_n = fac ? (long long)((n.HV + DZV_EXT) * (n.HW + 1) + DZV_EXT * (n.HV + 1)) : 0;
+    // (from the chunk queue's cursors in the header on: the weight-gradient launch needs them zero as well)
+    *zero_buf = fac ? (float*)(db + D.scale + DW_CURSOR_OFF) : nullptr;
+    *zero_n = fac ? (long long)((D.fac - D.scale - DW_CURSOR_OFF) / 4 + (n.HV + DZV_EXT) * (n.HW + 1) + DZV_EXT * (n.HV + 1)) : 0;
     return true;
 }
 }  // namespace lush

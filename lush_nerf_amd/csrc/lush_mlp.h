@@ -17,7 +17,8 @@ enum { NET_MAX_LAYERS = 8 };
 enum { PLANES_F16 = 17 };   // plane code: 1..3 = bf16 planes, 17 = ONE fp16 plane (forward of the NeRF nets)
 // kernel-variant bits of the C ABI (include/lush_march.h LUSH_VARIANT_*): 0 = the product's choice
 enum { LUSH_VARIANT_FWD_HALF = 1, LUSH_VARIANT_FWD_512 = 2, LUSH_VARIANT_BWD_512 = 4, LUSH_VARIANT_HEAD_KERNEL = 8, LUSH_VARIANT_BWD_HALF = 16,
-       LUSH_VARIANT_PE_ROWS = 64, LUSH_VARIANT_DW_SPLIT = 128, LUSH_VARIANT_DENSE_BWD = 256, LUSH_VARIANT_KERNEL_BITS = 0x3DF };
+       LUSH_VARIANT_PE_ROWS = 64, LUSH_VARIANT_DW_SPLIT = 128, LUSH_VARIANT_DENSE_BWD = 256, LUSH_VARIANT_DW_WALK = 512,
+       LUSH_VARIANT_KERNEL_BITS = 0x3DF };
 
 template <int HW_, int NL_, int SKIP_>
 struct NetT {
@@ -270,9 +271,24 @@ struct DwGroup {
                                    // workgroup b belongs to the job j with first[j] <= b < first[j + 1].  The slice counts are
                                    // proportional to the jobs' cost per point, so every workgroup is busy for the same time and
                                    // drains / flushes / refills ONCE (a walking workgroup does it per job: ten times)
-    int first[DW_MAX_JOBS + 1];    // per_job == 2: prefix sums of the jobs' slice counts
+                                   // 3: grid (splits) -- the chunk queue (launches above LUSH_DW_PERJOB_MAX_PTS points): the points are cut
+                                   // into chunks of LUSH_DW_QUEUE_CHUNK, job j hands its chunks out through cursor[j] (one returning
+                                   // atomicAdd per chunk), and a workgroup streams every chunk it can claim of ONE job into the same
+                                   // accumulators before it flushes and moves to the next job in rotation that has chunks left.
+                                   // Workgroup b starts on the job j with first[j] <= b < first[j + 1] (cost-proportional shares, as
+                                   // for 2), so few have to move: 2 - 3 drains / flushes / refills per workgroup instead of ten
+    int first[DW_MAX_JOBS + 1];    // per_job == 2: prefix sums of the jobs' slice counts; 3: of the workgroups that START on each job
     const int* live_cnt;           // live-point launches: the point count on the device (Ppad / pts_per_split are derived from it
                                    // in the kernel; the host's values are upper bounds), or null
+    int* cursor;                   // per_job == 3: [DW_MAX_JOBS] chunk cursors in device scratch, ZERO when the launch starts (the
+                                   // dstash header behind the loss scale: whoever zeroes the feature-factor scratch zeroes them)
 };
+// Points per chunk of the queue: a multiple of 2 * GRP_PE_CHUNK (the re-encoding jobs' coordinate prefetch stays chunk-aligned and
+// every chunk starts on coordinate buffer 0).  A workgroup streams ~30 ns per point: the chunk bounds the launch's tail.
+#ifndef LUSH_DW_QUEUE_CHUNK
+#define LUSH_DW_QUEUE_CHUNK 1024
+#endif
+// bytes of the dstash header in front of the cursors: {loss scale, 1 / scale, 2 work words of grad_scale_kernel}
+constexpr int DW_CURSOR_OFF = 16;
 
 }  // namespace lush

@@ -1065,11 +1065,34 @@ __device__ unsigned long long lush_prof_dw_span[2 * 1024];      // [b] start, [1
 #define DPROF_T(var)
 #define DPROF_ADD(slot, t0)
 #endif
-template <bool XF16, bool ZF16, int NV2, int NS>
+// Chunk queue (DwGroup::per_job == 3, Q below): where a workgroup's tiles come from.  The tiles of consecutive chunks are ONE tile
+// sequence through the ring -- only the source pointer jumps at a chunk's end -- so nothing drains between them.
+//  * Wave 0 / lane 0 claims the chunk AFTER the one it enters with one returning atomic, issued in front of the chunk's first tile.
+//    It sits in the same in-order vmcnt queue as the ring's DMAs and is not counted in the grp_wait<> constants: an undercount is
+//    safe (the waits get stricter), as for the coordinate DMAs.  Three tiles later 12 DMAs of the wave are younger than it, so a
+//    vmcnt(8) proves it back without stalling; the wave stores the id to the claim word in LDS, and one tile (one barrier) later
+//    every wave reads it into a scalar.  Chunks have at least 8 tiles (point counts are whole 256-point tiles), so the id is known
+//    long before the chunk ends.  The result lives in v255, which belongs to these two asm statements alone: handed a C++
+//    variable, the compiler copied the register right behind the atomic, before the value was back.  The kernel is compiled
+//    with amdgpu_num_vgpr(255), and isa_check rule R6 refuses a build in which anything else names v255.
+//  * The claim word is the unused fourth float of point 0 in the coordinate buffer the current tiles read from (the buffer the
+//    chunk DMAs do NOT write during these two tiles); launches without coordinate buffers get 16 bytes at the same place.  The
+//    re-encoding launch fills the CU's 160 KB of LDS to the byte, so there is no other room.
+//  * Nobody waits for anybody: a claim past the end ends the job for this workgroup (stream what is in flight, flush, move on).
+struct GrpQueue {
+    int* cursor;            // this job's cursor
+    int first;              // the chunk the workgroup has claimed already
+    int n_chunks;           // chunks of the launch
+    int last_tiles;         // tiles of the last chunk (every other chunk: LUSH_DW_QUEUE_CHUNK / points per tile)
+    unsigned claim_off;     // byte offset of coordinate buffer 0 behind `tiles`
+};
+static_assert(LUSH_DW_QUEUE_CHUNK % (2 * 512) == 0 && LUSH_DW_QUEUE_CHUNK >= 1024, "chunks are whole pairs of coordinate chunks");
+
+template <bool XF16, bool ZF16, int NV2, int NS, bool Q = false>
 __device__ __forceinline__ void grp_stream(const GrpStream& st, const char* tiles, unsigned lds0, int n_tiles, int w, int lane,
                                            bool wave_live, bool row_live, bool x2_wave, const unsigned (&a_off)[4],
                                            const unsigned (&b_off)[2], unsigned sel_off, const unsigned (&x2_off)[2],
-                                           f32x16 (&acc)[4][2], f32x16 (&accs)[2]) {
+                                           f32x16 (&acc)[4][2], f32x16 (&accs)[2], const GrpQueue& q = GrpQueue{}) {
     auto mm = [](bf16x8 a, bf16x8 b, f32x16 c) { return ZF16 ? mfma_f16(a, b, c) : mfma_bf16(a, b, c); };
     auto xcv = [](bf16x8 v) {
         if constexpr (XF16 && !ZF16) return f16_frag_to_bf16(v);
@@ -1085,23 +1108,55 @@ __device__ __forceinline__ void grp_stream(const GrpStream& st, const char* tile
     constexpr int KT_ = DMA_KT / NS;
     const char* coords = tiles + DMA_STAGES * GRP_STAGE;         // [2][GRP_PE_BYTES] (allocated when DwGroup::xd is given)
     int ti = 0;                                                   // tiles issued
-    auto pe_chunk = [&](int k) {      // this wave's 64 quadruples of chunk k -> LDS buffer k & 1 (one LDS-DMA, gathered: 32-byte stride)
+    auto pe_chunk = [&](int k, int buf) {      // this wave's 64 quadruples of chunk k -> LDS buffer `buf` (one LDS-DMA, gathered: 32-byte stride)
         long long pt = (long long)k * GRP_PE_CHUNK + w * 64 + lane;
         if (pt > st.pe_last) pt = st.pe_last;
-        dma16s(st.xd, (unsigned)(pt * 32), __builtin_amdgcn_readfirstlane(lds0 + (unsigned)(DMA_STAGES * GRP_STAGE + (k & 1) * GRP_PE_BYTES + w * 1024)));
+        dma16s(st.xd, (unsigned)(pt * 32), __builtin_amdgcn_readfirstlane(lds0 + (unsigned)(DMA_STAGES * GRP_STAGE + buf * GRP_PE_BYTES + w * 1024)));
     };
+    // queue mode: the chunk the issue side is in, the tile of it that is issued next, its tile count, the chunk after it (n_chunks:
+    // not known yet, or none) and, in wave 0 / lane 0, the register the claim returns to
+    constexpr int Q_TILES = LUSH_DW_QUEUE_CHUNK / KT_, Q_PE = LUSH_DW_QUEUE_CHUNK / GRP_PE_CHUNK;
+    int q_cur = 0, q_nt = 0, q_nxt = 0;
+    auto q_enter = [&](int c) {
+        q_cur = c; q_nxt = q.n_chunks;
+        q_nt = c == q.n_chunks - 1 ? q.last_tiles : Q_TILES;
+        src = st.src + (long long)c * Q_TILES * st.stride;
+        src2 = st.src2 + (long long)c * Q_TILES * st.stride2;
+    };
+    if constexpr (Q) q_enter(q.first);
     constexpr bool PE = XF16 && NS == 1;                          // the only stash format the encoding is recomputed for
     DPROF_T(t_pe0);
     if constexpr (NV2 > 0 && PE) {
         if (st.xd != nullptr) {       // chunk 0 before the first tile is issued (once per job: the only drain of the scheme)
-            pe_chunk(0);
+            pe_chunk(Q ? q.first * Q_PE : 0, 0);
             grp_wait<0>();
             asm volatile("s_waitcnt lgkmcnt(0)\n\ts_barrier" ::: "memory");
         }
     }
     DPROF_ADD(2, t_pe0);
-    auto issue = [&](int slot) {
+    // (queue mode: q_k = the tile's number inside its chunk; head = one of the chunk's first five tiles, which carry the claim)
+    auto issue = [&](int slot, int q_k = 0, bool head = false) {
         const unsigned base = lds0 + (unsigned)slot * GRP_STAGE;
+        if (Q && head) {
+            volatile int* claim = reinterpret_cast<volatile int*>(const_cast<char*>(tiles) + q.claim_off + ((ti >> 4) & 1) * GRP_PE_BYTES + 12);
+            if (q_k == 0) {
+                if (w == 0) {       // (lane 0 alone, by the exec mask inside the statement; s_nop: the cursor's address may come straight out
+                                    // of a scalar-spill reload, 5 wait states in front of a VMEM instruction -- isa_check rule R1)
+                    const unsigned zero = 0; const int one = 1;
+                    unsigned long long keep;
+                    asm volatile("s_mov_b64 %0, exec\n\ts_mov_b64 exec, 1\n\ts_nop 4\n\tglobal_atomic_add v255, %1, %2, %3 sc0\n\ts_mov_b64 exec, %0"
+                                 : "=&s"(keep) : "v"(zero), "v"(one), "s"(q.cursor) : "memory", "v255");
+                }
+            } else if (q_k == 3) {
+                if (w == 0) {
+                    unsigned long long keep;
+                    asm volatile("s_mov_b64 %0, exec\n\ts_mov_b64 exec, 1\n\ts_waitcnt vmcnt(8)\n\tds_write_b32 %1, v255\n\ts_mov_b64 exec, %0"
+                                 : "=&s"(keep) : "v"(lds0 + q.claim_off + (unsigned)(((ti >> 4) & 1) * GRP_PE_BYTES + 12)) : "memory");
+                }
+            } else if (q_k == 4) {
+                q_nxt = __builtin_amdgcn_readfirstlane(*claim);
+            }
+        }
 #pragma unroll
         for (int i = 0; i < 4; ++i)
             if (st.on[i]) dma16s_stream(src, st.voff[i], __builtin_amdgcn_readfirstlane(base + st.dst[i]));
@@ -1116,7 +1171,15 @@ __device__ __forceinline__ void grp_stream(const GrpStream& st, const char* tile
                 src2 += st.stride2;
             }
             if (PE && st.xd != nullptr) {      // every wave: its 64 points of the NEXT chunk when a chunk begins
-                if ((ti & 15) == 0) pe_chunk(ti / 16 + 1);
+                if constexpr (Q) {             // (behind a chunk's last coordinates come the next chunk's first, if there is one -- known
+                                               // from its fifth tile on)
+                    if ((ti & 15) == 0) {
+                        const bool inside = q_k + 16 < q_nt;
+                        if (inside || q_nxt < q.n_chunks) pe_chunk(inside ? q_cur * Q_PE + (q_k >> 4) + 1 : q_nxt * Q_PE, ((ti >> 4) + 1) & 1);
+                    }
+                } else {
+                    if ((ti & 15) == 0) pe_chunk(ti / 16 + 1, (ti / 16 + 1) & 1);
+                }
                 ++ti;
             }
         }
@@ -1182,6 +1245,34 @@ __device__ __forceinline__ void grp_stream(const GrpStream& st, const char* tile
         else grp_wait<0>();
     };
     DPROF_T(t_pro);
+    if constexpr (Q) {
+        // fill; per chunk its head tiles (the claim) and then the walk's steady loop, unchanged; on to the chunk the claim named, or
+        // drain.  The number of tiles is not known before the last claim comes back; every chunk has at least 8.
+        int slot = 0;
+        auto steady = [&](int k, bool head) {            // DMA_STAGES - 2 younger stages in flight behind the one awaited
+            if (five) grp_wait<5 * (DMA_STAGES - 2)>(); else grp_wait<4 * (DMA_STAGES - 2)>();
+            asm volatile("s_waitcnt lgkmcnt(0)\n\ts_barrier" ::: "memory");
+            issue(slot == 0 ? DMA_STAGES - 1 : slot - 1, k, head);
+            compute(slot);
+            slot = slot + 1 == DMA_STAGES ? 0 : slot + 1;
+        };
+        for (int t = 0; t < DMA_STAGES - 1; ++t) issue(t, t, true);
+        int k = DMA_STAGES - 1;
+        for (;;) {
+            for (; k < 5; ++k) steady(k, true);
+            for (; k < q_nt; ++k) steady(k, false);
+            if (q_nxt >= q.n_chunks) break;
+            q_enter(q_nxt);
+            k = 0;
+        }
+        for (int t = DMA_STAGES - 2; t >= 0; --t) {      // drain: nothing left to issue
+            wait_younger(t);
+            asm volatile("s_waitcnt lgkmcnt(0)\n\ts_barrier" ::: "memory");
+            compute(slot);
+            slot = slot + 1 == DMA_STAGES ? 0 : slot + 1;
+        }
+        return;
+    }
     for (int t = 0; t < DMA_STAGES - 1 && t < n_tiles; ++t) issue(t);
     int slot = 0;
     const int n_steady = n_tiles - (DMA_STAGES - 1);
@@ -1210,8 +1301,10 @@ __device__ __forceinline__ void grp_stream(const GrpStream& st, const char* tile
     DPROF_ADD(5, t_drain);
 }
 
-template <bool XF16, bool ZF16, int NS>
-__global__ __launch_bounds__(DW_THREADS2) void dw_group_kernel(const DwGroup G) {
+// One body, two kernels: dw_group_kernel (QUEUE = false: the walk, one job per workgroup -- every queue statement is compiled out,
+// so small launches and the kept walk run the code they always ran) and dw_group_kernel<.., 1> (DwGroup::per_job == 3).
+template <bool XF16, bool ZF16, int NS, bool QUEUE>
+__device__ __forceinline__ void dw_group_body(const DwGroup& G) {
     static_assert(DMA_STAGES >= 2 && DMA_STAGES <= 4, "the drain's wait table covers up to 4 stages");
     static_assert(NS == 1 || (NS == 2 && !XF16 && !ZF16), "two planes are bf16 planes");
     constexpr int KT = DMA_KT / NS;                 // points per stage
@@ -1225,7 +1318,7 @@ __global__ __launch_bounds__(DW_THREADS2) void dw_group_kernel(const DwGroup G) 
     // exactly as many workgroups as CUs puts 32 of them on each XCD under the dispatcher's round-robin: as a (slices, jobs)
     // grid with idle surplus workgroups some XCDs received 35 working ones, and the launch waited for their second round)
     int my_job = (int)blockIdx.y, my_slice = (int)blockIdx.x;
-    if (G.per_job == 2) {
+    if (G.per_job == 2 || (QUEUE && G.per_job == 3)) {      // (3, the chunk queue: the job this workgroup STARTS on)
         my_job = 0;
         for (int j = 1; j < G.n; ++j) my_job = (int)blockIdx.x >= G.first[j] ? j : my_job;
         my_slice = (int)blockIdx.x - G.first[my_job];
@@ -1236,7 +1329,7 @@ __global__ __launch_bounds__(DW_THREADS2) void dw_group_kernel(const DwGroup G) 
     if (G.live_cnt != nullptr) {
         const int cnt = __builtin_amdgcn_readfirstlane(*G.live_cnt);
         Ppad = (cnt + 255) / 256 * 256;                  // (the stash arrays of a launch are padded to whole 256-point tiles)
-        if (Ppad <= LUSH_DW_PERJOB_MAX_PTS && per_job == 0 && (int)gridDim.x >= G.n) {
+        if (Ppad <= LUSH_DW_PERJOB_MAX_PTS && (per_job == 0 || (QUEUE && per_job == 3)) && (int)gridDim.x >= G.n) {
             // few live points (a trained scene's empty space is dead): ONE job per workgroup on the 1-D grid, as the host chooses
             // for a small pass it knows the size of (lush_abi.hip) -- workgroup b = (slice b / n, job b mod n), just enough slices
             // to fill the chip once.  The walk's 256 slices x 10 jobs of fp32 atomics (0.6 GB at the chip's 1.3 TB/s: 0.45 ms
@@ -1254,11 +1347,17 @@ __global__ __launch_bounds__(DW_THREADS2) void dw_group_kernel(const DwGroup G) 
             pps = ((Ppad + (int)gridDim.x - 1) / (int)gridDim.x + 31) / 32 * 32;
         }
     }
-    const long long p_begin = (long long)my_slice * pps;
+    const bool queue = QUEUE && per_job == 3;      // every workgroup takes points from everywhere: no slice
+    const long long p_begin = queue ? 0 : (long long)my_slice * pps;
     long long p_end = p_begin + pps;
     if (p_end > Ppad) p_end = Ppad;
     const int n_tiles = (int)((p_end - p_begin) / KT);
-    if (n_tiles <= 0) return;
+    if (n_tiles <= 0 && !queue) return;
+    GrpQueue q;
+    q.cursor = nullptr; q.first = 0;
+    q.n_chunks = (Ppad + LUSH_DW_QUEUE_CHUNK - 1) / LUSH_DW_QUEUE_CHUNK;
+    q.last_tiles = (Ppad - (q.n_chunks - 1) * LUSH_DW_QUEUE_CHUNK) / KT;
+    q.claim_off = (unsigned)(DMA_STAGES * GRP_STAGE);
     const float unscale = ZF16 ? G.scale[1] : 1.f;
     const unsigned lds0 = (unsigned)(size_t)(__attribute__((address_space(3))) char*)tiles;
     const int r = lane & 31, h = lane >> 5;
@@ -1272,10 +1371,37 @@ __global__ __launch_bounds__(DW_THREADS2) void dw_group_kernel(const DwGroup G) 
 
     // (a small launch -- the 4 096-point noise net, configuration 1 -- has fewer slices than the chip has CUs and spent its time
     // walking 7-19 jobs in series, each a ring refill + a few tiles + 64 K atomics: 69 us for 0.4 GFLOP; one job per workgroup then)
-    const int j_begin = per_job ? my_job : 0, j_end = per_job ? my_job + 1 : G.n;
+    const bool one_job = QUEUE ? per_job == 1 || per_job == 2 : per_job != 0;
+    const int j_begin = one_job ? my_job : 0, j_end = one_job ? my_job + 1 : G.n;
     for (int jj = j_begin; jj < j_end; ++jj) {
-        int jsel = per_job ? jj : (int)((blockIdx.x + (unsigned)jj) % (unsigned)G.n);
+        int jsel = one_job ? jj : (int)(((queue ? (unsigned)my_job : blockIdx.x) + (unsigned)jj) % (unsigned)G.n);
         jsel = __builtin_amdgcn_readfirstlane(jsel);
+        if (queue) {
+            // The next job in rotation that still has chunks, and its first chunk for this workgroup.  Wave 0 looks at all the
+            // cursors at once (one load per lane; a stale value only costs a claim that fails), so jobs that are finished cost
+            // nothing -- no claim, no zeroing, no flush -- and a workgroup that finds none left ends after ONE round trip.
+            volatile int* claim = reinterpret_cast<volatile int*>(tiles + q.claim_off);      // [2]: jobs skipped (-1: none left), [3]: chunk
+            asm volatile("s_waitcnt lgkmcnt(0)\n\ts_barrier" ::: "memory");     // everyone has read the previous claim
+            if (w == 0) {
+                const bool left = lane < G.n && __hip_atomic_load(G.cursor + lane, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT) < q.n_chunks;
+                const unsigned long long live = __ballot(left);
+                int skip = -1;
+                for (int t = G.n - 1 - jj; t >= 0; --t)
+                    if ((live >> ((jsel + t) % G.n)) & 1) skip = t;
+                if (lane == 0) {
+                    claim[2] = skip;
+                    if (skip >= 0) claim[3] = atomicAdd(G.cursor + (jsel + skip) % G.n, 1);
+                }
+            }
+            asm volatile("s_waitcnt lgkmcnt(0)\n\ts_barrier" ::: "memory");
+            const int skip = __builtin_amdgcn_readfirstlane(claim[2]);
+            if (skip < 0) break;
+            jj += skip;
+            jsel = __builtin_amdgcn_readfirstlane((jsel + skip) % G.n);
+            q.first = __builtin_amdgcn_readfirstlane(claim[3]);
+            q.cursor = G.cursor + jsel;
+            if (q.first >= q.n_chunks) continue;
+        }
         const DwJob A = G.j[jsel];                      // one scalar load of the whole record per job
         const bool has_x2 = A.X2 != nullptr;
         const bool wave_live = (wo * 128 < A.n_out) && (wi * 64 < A.k_in);
@@ -1341,6 +1467,11 @@ __global__ __launch_bounds__(DW_THREADS2) void dw_group_kernel(const DwGroup G) 
                 st.on2 = gch * 8 < A.k2_in;
             }
         }
+        if (QUEUE && queue) {
+            if (nv2 == 0) grp_stream<XF16, ZF16, 0, NS, QUEUE>(st, tiles, lds0, 0, w, lane, wave_live, row_live, x2_wave, a_off, b_off, sel_off, x2_off, acc, accs, q);
+            else if (nv2 == 1) grp_stream<XF16, ZF16, 1, NS, QUEUE>(st, tiles, lds0, 0, w, lane, wave_live, row_live, x2_wave, a_off, b_off, sel_off, x2_off, acc, accs, q);
+            else grp_stream<XF16, ZF16, 2, NS, QUEUE>(st, tiles, lds0, 0, w, lane, wave_live, row_live, x2_wave, a_off, b_off, sel_off, x2_off, acc, accs, q);
+        } else
         if (nv2 == 0) grp_stream<XF16, ZF16, 0, NS>(st, tiles, lds0, n_tiles, w, lane, wave_live, row_live, x2_wave, a_off, b_off, sel_off, x2_off, acc, accs);
         else if (nv2 == 1) grp_stream<XF16, ZF16, 1, NS>(st, tiles, lds0, n_tiles, w, lane, wave_live, row_live, x2_wave, a_off, b_off, sel_off, x2_off, acc, accs);
         else grp_stream<XF16, ZF16, 2, NS>(st, tiles, lds0, n_tiles, w, lane, wave_live, row_live, x2_wave, a_off, b_off, sel_off, x2_off, acc, accs);
@@ -1391,6 +1522,13 @@ __global__ __launch_bounds__(DW_THREADS2) void dw_group_kernel(const DwGroup G) 
     if (threadIdx.x == 0 && blockIdx.x < 1024 && blockIdx.y == 0) { lush_prof_dw_span[blockIdx.x] = t_kernel; lush_prof_dw_span[1024 + blockIdx.x] = __builtin_amdgcn_s_memtime(); }
 #endif
 }
+
+template <bool XF16, bool ZF16, int NS>
+__global__ __launch_bounds__(DW_THREADS2) void dw_group_kernel(const DwGroup G) { dw_group_body<XF16, ZF16, NS, false>(G); }
+// (255 VGPRs: v255 belongs to the claim's asm statements -- GrpQueue above, isa_check rule R6)
+// (an overload with one more template argument, so that profiles keep finding every grouped launch under one name)
+template <bool XF16, bool ZF16, int NS, int QUEUE>
+__global__ __launch_bounds__(DW_THREADS2) __attribute__((amdgpu_num_vgpr(255))) void dw_group_kernel(const DwGroup G) { static_assert(QUEUE == 1, ""); dw_group_body<XF16, ZF16, NS, true>(G); }
 
 // Loss scale of the fp16 gradient chain: scale = 2^k with max|d_raw| * scale in [8, 16) (gradients grow by at most
 // ~2^5 through the heads of the sharpest test networks; fp16 tops out at 2^16), 1 when d_raw is all zero or not
@@ -1730,8 +1868,9 @@ int launch_dw(int ns, const DwArgs& a, int splits, hipStream_t s) {
 
 template <bool XF16, bool ZF16, int NS>
 static int launch_dw_group_t(const DwGroup& g, int splits, hipStream_t s) {
-    const size_t lds = (size_t)DMA_STAGES * GRP_STAGE + (g.xd ? 2 * GRP_PE_BYTES : 0);
-    auto k = dw_group_kernel<XF16, ZF16, NS>;
+    // (the chunk queue without coordinate buffers: 16 bytes where they would begin, for its claim word)
+    const size_t lds = (size_t)DMA_STAGES * GRP_STAGE + (g.xd ? 2 * GRP_PE_BYTES : (g.per_job == 3 ? 16 : 0));
+    auto k = g.per_job == 3 ? dw_group_kernel<XF16, ZF16, NS, 1> : dw_group_kernel<XF16, ZF16, NS>;
     LUSH_HIP(hipFuncSetAttribute(reinterpret_cast<const void*>(k), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
     hipLaunchKernelGGL(k, dim3(splits, g.per_job == 1 ? g.n : 1), dim3(DW_THREADS2), lds, s, g);
     LUSH_HIP(hipGetLastError());
@@ -1764,6 +1903,7 @@ int launch_dw_group(const DwGroup& g, int splits, int ns, bool x_f16, bool z_f16
         if (j.X2 && (j.k2_in < 8 || j.k2_in > 63 || j.k2_in % 32 == 0)) return set_error("launch_dw_group: second input block must leave its last column free");
     }
     if (g.pts_per_split % DMA_KT != 0 || g.Ppad % DMA_KT != 0) return set_error("launch_dw_group: slices are whole 32-point tiles");
+    if (g.per_job == 3 && (g.cursor == nullptr || g.Ppad % 256 != 0 || g.first[g.n] != splits)) return set_error("launch_dw_group: the chunk queue needs its cursors, whole 256-point tiles and one starting job per workgroup");
     if (ns == 2) {
         if (x_f16 || z_f16) return set_error("launch_dw_group: two planes are bf16 planes");
         return launch_dw_group_t<false, false, 2>(g, splits, s);

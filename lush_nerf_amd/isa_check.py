@@ -19,6 +19,11 @@ states after the previous MFMA, so MFMAs in between age a producer by their pass
   R5  A VGPR that an outstanding VMEM load will write is read or written before an `s_waitcnt vmcnt(N)` has retired that
       load (vmcnt retires in issue order; stores and LDS-DMAs count) -- this validates every hand-counted vmcnt(N) behind
       an asm load, including across the loop back-edge.
+  R6  The chunk queue (dw_group_kernel<.., 1>) claims a chunk with a returning atomic whose result comes back three tiles later, in
+      the same in-order vmcnt queue as the ring's LDS-DMAs.  The compiler would copy a register it believes written (it did:
+      the copy read the register before the value was back), so the result lives in v255, which the kernel's
+      amdgpu_num_vgpr(255) keeps out of the compiler's hands.  In these kernels v255 may be named only as the destination of
+      `global_atomic_add ... sc0` and as the data of a `ds_write_b32` directly behind an `s_waitcnt vmcnt(N)`, N <= 8.
 Control flow: every path is followed (a worklist over (instruction, state), both sides of every conditional branch), so a
 producer at the end of a loop body meets the consumer at its head.
 """
@@ -35,6 +40,7 @@ LLVM_BIN = "/opt/rocm/lib/llvm/bin"
 # load is hidden from the compiler's own s_waitcnt bookkeeping: the kernels of the source files that hold an asm VMEM load
 # into registers (tests/test_cpu_host.py checks this list against the sources).
 R5_KERNELS = ("mlp_wide_bwd_kernel",)
+R6_KERNELS = {r"dw_group_kernelILb[01]ELb[01]ELi\d+ELi1EEE": 255}      # (mangled) kernel name pattern -> the VGPR its asm statements own
 PK_F32_TO_MFMA = 4          # tools/micro/hazards.hip P2 measures what the hardware needs; see DESIGN.md section 4
 _REG = re.compile(r"\b([vsa])(?:\[(\d+):(\d+)\]|(\d+))")
 _VALU_SDST_FIRST = ("v_readlane_b32", "v_readfirstlane_b32")
@@ -263,14 +269,36 @@ def _step(st: _State, k: int, insts: List[Inst], kernel: str, found: set, r5: bo
     return _State(recent, vm, pipe)
 
 
+def _check_reserved(name: str, insts: List[Inst], reg: int) -> List[str]:
+    """R6: the reserved VGPR is named by the claim's two statements only, and read only behind a counted wait."""
+    out = []
+    for k, i in enumerate(insts):
+        if not any(reg in _regs(o, "v") for o in i.ops):
+            continue
+        me = f"v{reg}"
+        if i.op == "global_atomic_add" and i.ops[0] == me and me not in [o.split()[0] for o in i.ops[1:]] and "sc0" in i.text:
+            continue
+        if i.op == "ds_write_b32" and len(i.ops) >= 2 and i.ops[1].split()[0] == me and i.ops[0] != me:
+            p = insts[k - 1] if k else None
+            if p is not None and p.op == "s_waitcnt" and p.vmcnt is not None and p.vmcnt <= 8:
+                continue
+            out.append(f"R6: {name}: `{i.text}` @{i.addr:#x} reads {me} without a counted `s_waitcnt vmcnt` in front of it")
+            continue
+        out.append(f"R6: {name}: `{i.text}` @{i.addr:#x} touches {me}, which belongs to the chunk queue's claim")
+    return out
+
+
 def check_kernel(name: str, insts: List[Inst], max_states: int = 2_000_000) -> List[str]:
     """Every path through the kernel, by a worklist over (instruction, state) with states merged by equality: both sides of
     every conditional branch are followed, so a producer at the end of a loop body meets the consumer at its head."""
     for i in insts:
         i.analyse()
     r5 = any(n in name for n in R5_KERNELS)
-    index = {i.addr: k for k, i in enumerate(insts)}
     found: set = set()
+    for part, reg in R6_KERNELS.items():
+        if re.search(part, name):
+            found |= set(_check_reserved(name, insts, reg))
+    index = {i.addr: k for k, i in enumerate(insts)}
     seen = set()
     work = [(0, _State())]
     steps = 0

@@ -193,7 +193,7 @@ def live_backward(precision: "Precision", hooks: Optional["Hooks"]) -> bool:
     csrc/lush_march_abi.hip live_mode): one or two planes each way (the three-plane reference mode keeps the backward over all
     the points), the product's kernels, and no test hook that wants every point's stash."""
     older = lib.VARIANT_FWD_HALF | lib.VARIANT_FWD_512 | lib.VARIANT_BWD_HALF | lib.VARIANT_BWD_512 | lib.VARIANT_PE_ROWS | \
-        lib.VARIANT_HEAD_KERNEL | lib.VARIANT_DW_SPLIT | lib.VARIANT_DENSE_BWD
+        lib.VARIANT_HEAD_KERNEL | lib.VARIANT_DW_SPLIT | lib.VARIANT_DW_WALK | lib.VARIANT_DENSE_BWD
     chain = (1, 2, PLANES_F16)
     return precision.fwd in chain and precision.bwd in chain and not (int(precision.variant) & older) and \
         (hooks is None or hooks.keep is None)
