@@ -592,12 +592,7 @@ static int mlp_bwd_impl(int net, int planes_f, int planes_b, const float* rays, 
                 DwJob& j = job(dzp[l], n.HW, n.HW, H(l - 1), n.HW, 0, n.HW, g->w[l], XV + n.HW, XV, g->b[l]);
                 with_pe(j, 0, XV, g->w[l], XV + n.HW, 0);
             } else {
-                DwJob& j = job(dzp[l], n.HW, n.HW, H(l - 1), n.HW, 0, n.HW, g->w[l], n.HW, 0, g->b[l]);
-#ifdef LUSH_ABL_H0
-                if (l == 1) j.pe_mode = 9;
-#else
-                (void)j;
-#endif
+                job(dzp[l], n.HW, n.HW, H(l - 1), n.HW, 0, n.HW, g->w[l], n.HW, 0, g->b[l]);
             }
         }
         // feature + views layers: G = dZv^T h_{NL-1} and s = sum dZv into scratch (launch_feat_factor below turns them

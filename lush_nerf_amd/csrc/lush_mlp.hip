@@ -169,12 +169,7 @@ __device__ __forceinline__ void seg_gemm(f32x16 (&acc)[RB][CB], const bf16x8* __
         for (int i = 0; i < RB; ++i)
 #pragma unroll
             for (int cb = 0; cb < CB; ++cb) {
-#ifdef LUSH_ABL_NOMFMA   // timing ablation only (wrong results): keep the operand loads, drop the MFMAs
-#pragma unroll
-                for (int p = 0; p < NS; ++p) asm volatile("" ::"v"(as[i][p]), "v"(bs[cb][p]));
-#else
                 acc[i][cb] = mfma_planes<NS, DT>(as[i], bs[cb], acc[i][cb]);
-#endif
             }
     };
 #pragma unroll
@@ -224,10 +219,6 @@ __device__ __forceinline__ void store_block(const f32x16& acc, char* img, int pl
                                             int pt, int rb, int lane, __bf16* stash, long long stash_plane,
                                             int stash_ld, long long gpt, unsigned long long* mask_words) {
     const int h = lane >> 5;
-#ifdef LUSH_ABL_NOEPI   // timing ablation only (wrong results)
-    asm volatile("" ::"v"(acc));
-    return;
-#endif
     if (RELU && mask_words != nullptr) {
         unsigned bits = 0;
 #pragma unroll
@@ -266,15 +257,10 @@ __device__ __noinline__ void copy_out(const char* img, int plane_bytes, int row_
     for (int i = tid; i < planes * MT * cpr; i += nthreads) {
         const int c = i % cpr, pt = (i / cpr) % MT, p = i / (cpr * MT);
         const uint4 v = *reinterpret_cast<const uint4*>(img + p * plane_bytes + swz(pt, c, row_bytes));
-#ifndef LUSH_NO_NT_STASH   // write-once stream: non-temporal stores (-2 % forward time)
-        {
-            typedef __attribute__((ext_vector_type(4))) unsigned int u32x4;
-            u32x4 vv = {v.x, v.y, v.z, v.w};
-            __builtin_nontemporal_store(vv, reinterpret_cast<u32x4*>(stash + p * stash_plane + (pt0 + pt) * stash_ld + c * 8));
-        }
-#else
-        *reinterpret_cast<uint4*>(stash + p * stash_plane + (pt0 + pt) * stash_ld + c * 8) = v;
-#endif
+        // non-temporal: write-once stream, -2 % forward time
+        typedef __attribute__((ext_vector_type(4))) unsigned int u32x4;
+        u32x4 vv = {v.x, v.y, v.z, v.w};
+        __builtin_nontemporal_store(vv, reinterpret_cast<u32x4*>(stash + p * stash_plane + (pt0 + pt) * stash_ld + c * 8));
     }
 }
 
@@ -393,9 +379,6 @@ __global__ __launch_bounds__(NW * 64) void mlp_fwd_kernel(const MlpFwdArgs A) {
 #pragma unroll 1
         for (int l = 1; l < NL; ++l) {
             LUSH_FRESH_LANE();
-#ifdef LUSH_STASH_EARLY
-            if (stash_on) copy_out_fast<MT, HW, NTHREADS>(actimg, ACT_PLANE, ACT_ROW, A.h0 + (l - 1) * A.h_stride, A.plane_h, pt0, tid, A.stash_planes);
-#endif
             if (trunk_active) {
                 acc_bias<RB, CB>(acc, f32 + N::f32_b_trunk + l * HW, rb0, HW, h);
                 if (l == N::SKIP)
@@ -404,9 +387,7 @@ __global__ __launch_bounds__(NW * 64) void mlp_fwd_kernel(const MlpFwdArgs A) {
                 seg_gemm<NS, RB, CB, N::KKH, DT>(acc, seg(N::fwd_L(l, true)), N::NRB, rb0, actimg, ACT_PLANE, ACT_ROW, 0,
                                              lane);
             }
-#ifndef LUSH_STASH_EARLY
             if (stash_on) copy_out_fast<MT, HW, NTHREADS>(actimg, ACT_PLANE, ACT_ROW, A.h0 + (l - 1) * A.h_stride, A.plane_h, pt0, tid, A.stash_planes);
-#endif
             lds_barrier();
             if (trunk_active) {
 #pragma unroll
@@ -1056,15 +1037,6 @@ __device__ __forceinline__ void dw_pe_write4(char* dst, const f32x4 c, int gch, 
 // The streaming loop of one job, specialised on the number of 32-column X2 blocks (0: none, the side accumulator is the
 // bias alone).  Nothing in it depends on the job except through `st` (registers) and three wave-uniform flags.
 LUSH_CLOCK_DECL(lush_clock_dw)
-#ifdef LUSH_PROF_DW   // developer build: s_memtime counts of workgroup 0 / thread 0 per phase of a job, read back through lush_debug_prof_dw
-__device__ unsigned long long lush_prof_dw[16];
-__device__ unsigned long long lush_prof_dw_span[2 * 1024];      // [b] start, [1024 + b] end of workgroup b (s_memtime: one clock for the chip)
-#define DPROF_T(var) const unsigned long long var = __builtin_amdgcn_s_memtime()
-#define DPROF_ADD(slot, t0) do { if (blockIdx.x == 0 && threadIdx.x == 0) lush_prof_dw[slot] += __builtin_amdgcn_s_memtime() - (t0); } while (0)
-#else
-#define DPROF_T(var)
-#define DPROF_ADD(slot, t0)
-#endif
 // Chunk queue (DwGroup::per_job == 3, Q below): where a workgroup's tiles come from.  The tiles of consecutive chunks are ONE tile
 // sequence through the ring -- only the source pointer jumps at a chunk's end -- so nothing drains between them.
 //  * Wave 0 / lane 0 claims the chunk AFTER the one it enters with one returning atomic, issued in front of the chunk's first tile.
@@ -1125,7 +1097,6 @@ __device__ __forceinline__ void grp_stream(const GrpStream& st, const char* tile
     };
     if constexpr (Q) q_enter(q.first);
     constexpr bool PE = XF16 && NS == 1;                          // the only stash format the encoding is recomputed for
-    DPROF_T(t_pe0);
     if constexpr (NV2 > 0 && PE) {
         if (st.xd != nullptr) {       // chunk 0 before the first tile is issued (once per job: the only drain of the scheme)
             pe_chunk(Q ? q.first * Q_PE : 0, 0);
@@ -1133,7 +1104,6 @@ __device__ __forceinline__ void grp_stream(const GrpStream& st, const char* tile
             asm volatile("s_waitcnt lgkmcnt(0)\n\ts_barrier" ::: "memory");
         }
     }
-    DPROF_ADD(2, t_pe0);
     // (queue mode: q_k = the tile's number inside its chunk; head = one of the chunk's first five tiles, which carry the claim)
     auto issue = [&](int slot, int q_k = 0, bool head = false) {
         const unsigned base = lds0 + (unsigned)slot * GRP_STAGE;
@@ -1244,7 +1214,6 @@ __device__ __forceinline__ void grp_stream(const GrpStream& st, const char* tile
         else if (younger == 1) { if (five) grp_wait<5>(); else grp_wait<4>(); }
         else grp_wait<0>();
     };
-    DPROF_T(t_pro);
     if constexpr (Q) {
         // fill; per chunk its head tiles (the claim) and then the walk's steady loop, unchanged; on to the chunk the claim named, or
         // drain.  The number of tiles is not known before the last claim comes back; every chunk has at least 8.
@@ -1276,29 +1245,19 @@ __device__ __forceinline__ void grp_stream(const GrpStream& st, const char* tile
     for (int t = 0; t < DMA_STAGES - 1 && t < n_tiles; ++t) issue(t);
     int slot = 0;
     const int n_steady = n_tiles - (DMA_STAGES - 1);
-#ifdef LUSH_PROF_DW
-    bool first = true;
-#endif
-    DPROF_T(t_steady0);
     for (int t = 0; t < n_steady; ++t) {            // DMA_STAGES - 2 younger stages in flight behind the one awaited
         if (five) grp_wait<5 * (DMA_STAGES - 2)>(); else grp_wait<4 * (DMA_STAGES - 2)>();
         asm volatile("s_waitcnt lgkmcnt(0)\n\ts_barrier" ::: "memory");
-#ifdef LUSH_PROF_DW
-        if (first) { DPROF_ADD(3, t_pro); first = false; }
-#endif
         issue(slot == 0 ? DMA_STAGES - 1 : slot - 1);
         compute(slot);
         slot = slot + 1 == DMA_STAGES ? 0 : slot + 1;
     }
-    DPROF_ADD(4, t_steady0);
-    DPROF_T(t_drain);
     for (int t = n_steady < 0 ? 0 : n_steady; t < n_tiles; ++t) {     // drain: nothing left to issue
         wait_younger(n_tiles - 1 - t);
         asm volatile("s_waitcnt lgkmcnt(0)\n\ts_barrier" ::: "memory");
         compute(slot);
         slot = slot + 1 == DMA_STAGES ? 0 : slot + 1;
     }
-    DPROF_ADD(5, t_drain);
 }
 
 // One body, two kernels: dw_group_kernel (QUEUE = false: the walk, one job per workgroup -- every queue statement is compiled out,
@@ -1312,7 +1271,6 @@ __device__ __forceinline__ void dw_group_body(const DwGroup& G) {
     const int tid = threadIdx.x, lane = tid & 63;
     const int w = __builtin_amdgcn_readfirstlane(tid >> 6);
     const int wo = w >> 2, wi = w & 3;
-    DPROF_T(t_kernel);
     LUSH_CLOCK_STAMP(lush_clock_dw, 0);
     // per_job == 2: a flat grid; this workgroup's job and slice from the prefix sums of the jobs' slice counts (a flat grid of
     // exactly as many workgroups as CUs puts 32 of them on each XCD under the dispatcher's round-robin: as a (slices, jobs)
@@ -1407,7 +1365,6 @@ __device__ __forceinline__ void dw_group_body(const DwGroup& G) {
         const bool wave_live = (wo * 128 < A.n_out) && (wi * 64 < A.k_in);
         const bool row_live = wo * 128 + wi * 32 < A.n_out;           // this wave's 32 rows of the bias / X2 blocks
         const int nv2 = has_x2 ? (A.k2_in > 32 ? 2 : 1) : 0;
-        DPROF_T(t_zero);
         // columns beyond a job's widths are never written by its DMAs: start every job from a zeroed ring
         asm volatile("s_waitcnt lgkmcnt(0)\n\ts_barrier" ::: "memory");     // everyone has left the previous job's tiles
         for (int i = tid; i < DMA_STAGES * GRP_STAGE / 16; i += DW_THREADS2)
@@ -1422,7 +1379,6 @@ __device__ __forceinline__ void dw_group_body(const DwGroup& G) {
             for (int a = 0; a < 4; ++a) { acc[a][0][q] = 0.f; acc[a][1][q] = 0.f; }
             accs[0][q] = 0.f; accs[1][q] = 0.f;
         }
-        DPROF_ADD(1, t_zero);
         const int bias_blk = nv2 ? nv2 - 1 : 0;                    // block that carries the bias column (its column 31)
         const bool x2_wave = has_x2 && w < 4;          // waves 0..3 move the four 1-KiB pieces of the X2 tile
         GrpStream st;
@@ -1441,9 +1397,6 @@ __device__ __forceinline__ void dw_group_body(const DwGroup& G) {
                 st.voff[i] = (unsigned)(((row % KT) * ld + gch * 8) * 2);
                 st.dst[i] = (unsigned)(op * DMA_OPER + 2 * rp * DMA_ROWB);
                 st.on[i] = gch * 8 < ncols;
-#ifdef LUSH_ABL_H0      // timing ablation only (wrong results): the job marked pe_mode 9 (layer 1: X = h_0) streams no X
-                if (op && A.pe_mode == 9) st.on[i] = false;
-#endif
             }
             st.src2 = nullptr; st.stride2 = 0; st.voff2 = 0; st.dst2 = 0; st.on2 = false;
             st.xd = nullptr; st.pe_last = 0; st.pe_row16 = 0; st.pe_dst = 0; st.pe_gch = 0; st.pe_nvalid = 0;
@@ -1475,11 +1428,6 @@ __device__ __forceinline__ void dw_group_body(const DwGroup& G) {
         if (nv2 == 0) grp_stream<XF16, ZF16, 0, NS>(st, tiles, lds0, n_tiles, w, lane, wave_live, row_live, x2_wave, a_off, b_off, sel_off, x2_off, acc, accs);
         else if (nv2 == 1) grp_stream<XF16, ZF16, 1, NS>(st, tiles, lds0, n_tiles, w, lane, wave_live, row_live, x2_wave, a_off, b_off, sel_off, x2_off, acc, accs);
         else grp_stream<XF16, ZF16, 2, NS>(st, tiles, lds0, n_tiles, w, lane, wave_live, row_live, x2_wave, a_off, b_off, sel_off, x2_off, acc, accs);
-        DPROF_T(t_flush);
-#ifdef LUSH_ABL_NOFLUSH      // timing ablation only (wrong results): the accumulators are kept alive, nothing is added
-        asm volatile("" ::"v"(acc[0][0]), "v"(acc[0][1]), "v"(acc[1][0]), "v"(acc[1][1]), "v"(acc[2][0]), "v"(acc[2][1]), "v"(acc[3][0]), "v"(acc[3][1]), "v"(accs[0]), "v"(accs[1]));
-        if (false)
-#endif
         if (row_live) {
 #pragma unroll
             for (int v = 0; v < 2; ++v) {
@@ -1496,9 +1444,6 @@ __device__ __forceinline__ void dw_group_body(const DwGroup& G) {
                 }
             }
         }
-#ifdef LUSH_ABL_NOFLUSH
-        if (false)
-#endif
         if (wave_live) {
 #pragma unroll
             for (int u = 0; u < 4; ++u)
@@ -1511,16 +1456,8 @@ __device__ __forceinline__ void dw_group_body(const DwGroup& G) {
                         if (o < A.n_out && i < A.k_in) atomicAdd(A.dW + (long long)o * A.ldw + A.wcol0 + i, acc[u][v][q] * unscale);
                     }
         }
-        DPROF_ADD(6, t_flush);
-#ifdef LUSH_PROF_DW
-        if (blockIdx.x == 0 && threadIdx.x == 0) lush_prof_dw[8] += 1;
-#endif
     }
-    DPROF_ADD(0, t_kernel);
     LUSH_CLOCK_STAMP(lush_clock_dw, 1);
-#ifdef LUSH_PROF_DW
-    if (threadIdx.x == 0 && blockIdx.x < 1024 && blockIdx.y == 0) { lush_prof_dw_span[blockIdx.x] = t_kernel; lush_prof_dw_span[1024 + blockIdx.x] = __builtin_amdgcn_s_memtime(); }
-#endif
 }
 
 template <bool XF16, bool ZF16, int NS>
@@ -1877,21 +1814,6 @@ static int launch_dw_group_t(const DwGroup& g, int splits, hipStream_t s) {
     return 0;
 }
 LUSH_CLOCK_EXPORT(lush_debug_clock_dw, lush_clock_dw)
-#ifdef LUSH_PROF_DW
-}  // namespace lush
-extern "C" int lush_debug_prof_dw(unsigned long long* out, int reset) {
-    LUSH_HIP(hipDeviceSynchronize());
-    LUSH_HIP(hipMemcpyFromSymbol(out, HIP_SYMBOL(lush::lush_prof_dw), sizeof(unsigned long long) * 16));
-    if (reset) { unsigned long long z[16] = {}; LUSH_HIP(hipMemcpyToSymbol(HIP_SYMBOL(lush::lush_prof_dw), z, sizeof(z))); }
-    return 0;
-}
-extern "C" int lush_debug_prof_dw_span(unsigned long long* out) {
-    LUSH_HIP(hipDeviceSynchronize());
-    LUSH_HIP(hipMemcpyFromSymbol(out, HIP_SYMBOL(lush::lush_prof_dw_span), sizeof(unsigned long long) * 2048));
-    return 0;
-}
-namespace lush {
-#endif
 // one launch for all the weight-gradient GEMMs of a network pass (ns = 1: one 16-bit plane per operand; 2: two bf16 planes)
 int launch_dw_group(const DwGroup& g, int splits, int ns, bool x_f16, bool z_f16, hipStream_t s) {
     for (int i = 0; i < g.n; ++i) {

@@ -97,15 +97,6 @@ struct ChSched {
     static constexpr int WRAP = 0;          // trunk positions never wrap: the tail follows them
 };
 
-#ifdef LUSH_PROF   // developer build: cycle counts (s_memtime) of block 0 / wave 0, read back with hipMemcpyFromSymbol
-__device__ unsigned long long lush_prof[8];
-#define PROF_T(var) const unsigned long long var = __builtin_amdgcn_s_memtime()
-#define PROF_ADD(slot, t0) prof[slot] += __builtin_amdgcn_s_memtime() - (t0)
-#else
-#define PROF_T(var)
-#define PROF_ADD(slot, t0)
-#endif
-
 // Row length of the dZv stash: one plane carries DZV_EXT more columns (lush_mlp.h)
 template <int NS, int HV>
 struct DzvLd { static constexpr int v = HV + (NS == 1 ? DZV_EXT : 0); };
@@ -231,13 +222,7 @@ struct ChPhase {
     static __device__ __forceinline__ void st_store(const Stash& st, const Regs& r, int job, int i, int lane) {
         const int j = job / SP, p = job % SP;
         u32x4* dst = reinterpret_cast<u32x4*>(st.rows + p * st.plane + (long long)(8 * i + (lane >> 3)) * LD + j * 64 + (lane & 7) * 8);
-#if defined(LUSH_ABL_NOSTORE)     // timing ablation only
-        asm volatile("" ::"v"(r.sb[i]), "v"(dst));
-#elif defined(LUSH_ABL_PLAINST)
-        *dst = r.sb[i];
-#else
         __builtin_nontemporal_store(r.sb[i], dst);
-#endif
     }
 
     // ---- half 1 of position I: MFMAs on a0; fillers: read a1 (units H..U-1), then a job's global stores ----
@@ -282,9 +267,6 @@ struct ChPhase {
                     const bool is_dma = (k < 2 * PAIRS) ? (k % 2 == 0) : (ND > NL);
                     const int d = (k < 2 * PAIRS) ? k / 2 : k - PAIRS;
                     if (is_dma) {
-#if defined(LUSH_ABL_NODMA)     // timing ablation only (wrong results): the refill DMAs are not issued
-                        (void)dma_off; (void)dma_dst;
-#else
                         // pieces go in pairs under one M0 save/restore (the odd one of a pair is a no-op filler)
                         if (d % 2 == 0) {
                             if (d + 1 < ND)
@@ -293,7 +275,6 @@ struct ChPhase {
                             else
                                 dma16s(cx.gbase + dma_off, cx.voff[d], __builtin_amdgcn_readfirstlane(dma_dst + (unsigned)d * 4096u));
                         }
-#endif
                     } else {
                         r.a0[d / NS][d % NS] = *reinterpret_cast<const bf16x8*>(rd_next + d * 1024 + cx.lane * 16);
                     }
@@ -334,18 +315,8 @@ struct ChPhase {
         h1<I>(acc, r, xin, cx.ring + cx.cslot * SC::SLOT, lane, st, std::make_integer_sequence<int, NM>{});
         // mid-step: my pieces of position +1 have landed; after the barrier everyone's have, and nobody
         // reads this position's slot any more (a1 is in registers: lgkmcnt(0) inside lds_barrier)
-#ifndef LUSH_ABL_NOVMWAIT   // timing ablations only (wrong results)
-#ifdef LUSH_ABL_OLDWAIT
-        wait_vm<TRUNK ? SC::trunk_wait : SC::tail_wait(T0 + I)>();
-#else
         wait_vm<(TRUNK ? SC::trunk_wait : SC::tail_wait(T0 + I)) + younger_stores(I)>();
-#endif
-#endif
-#ifndef LUSH_ABL_NOBAR
         lds_barrier();
-#else
-        asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
-#endif
         const unsigned dma_dst = __builtin_amdgcn_readfirstlane(cx.ring_lds + (unsigned)cx.cslot * SC::SLOT + (unsigned)cx.w * 1024u);
         unsigned dma_off;
         if constexpr (TRUNK) {
@@ -416,19 +387,6 @@ template <int NS, int DT, bool RELU, int NB, int KX, bool MASK, bool REBIAS = fa
 __device__ __forceinline__ void ch_convert(f32x16 (&acc)[NB], bf16x8 (&xin)[KX][NS], unsigned short* mrow, int lane,
                                            const float* __restrict__ nextb = nullptr) {
     static_assert(2 * NB <= KX, "activation planes do not fit");
-#ifdef LUSH_ABL_NOCONV   // timing ablation only (wrong results): register moves instead of ReLU + plane split
-#pragma unroll
-    for (int rb = 0; rb < NB; ++rb)
-#pragma unroll
-        for (int t = 0; t < 2; ++t)
-#pragma unroll
-            for (int p = 0; p < NS; ++p) {
-                f32x4 v = {acc[rb][8 * t], acc[rb][8 * t + 1 + p], acc[rb][8 * t + 2], acc[rb][8 * t + 3 + p]};
-                asm volatile("" : "+v"(v));
-                xin[2 * rb + t][p] = __builtin_bit_cast(bf16x8, v);
-            }
-    return;
-#endif
     typedef __attribute__((ext_vector_type(4))) unsigned int u32x4;
 #pragma unroll
     for (int rb = 0; rb < NB; ++rb) {
@@ -548,18 +506,11 @@ __global__ __launch_bounds__(CH_NT) void mlp_chain_fwd_kernel(const MlpFwdArgs A
     const int row = w * 32 + n;
     char* tile_w = stage + w * 4096;
 
-#ifdef LUSH_PROF
-    unsigned long long prof[8] = {0, 0, 0, 0, 0, 0, 0, 0};
-    const unsigned long long t_kernel = __builtin_amdgcn_s_memtime();
-#endif
     for (int tile = blockIdx.x; tile < n_tiles; tile += gridDim.x) {
         const long long pt0 = (long long)tile * CH_MT;
         const long long gpt = pt0 + row;
-        PROF_T(t_pe);
         const long long wpt = pt0 + w * 32;            // this wave's first point
-#ifndef LUSH_ABL_NOPE    // timing ablation only (wrong results)
         pe_tile<NS, CH_MT, CH_NT, DT>(peimg, PE_PLANE, PE_ROW * 2, A.rays, A.z, A.S, P, pt0, tid, A.live_idx);
-#endif
         wait_vm<0>();      // first tile: the prologue DMAs; later tiles: already published by the last mid-step
         lds_barrier();
         if (stash_on) {
@@ -569,7 +520,6 @@ __global__ __launch_bounds__(CH_NT) void mlp_chain_fwd_kernel(const MlpFwdArgs A
                 *reinterpret_cast<uint4*>(A.pe + p * A.plane_pe + (pt0 + pt) * PE_ROW + c * 8) = v;
             }
         }
-        PROF_ADD(1, t_pe);
         cx.trunk_pos = 0;
         {   // opaque per tile: otherwise the ~40 static stream addresses of the tail are hoisted out of the
             // tile loop and live (spilled) across it
@@ -588,22 +538,16 @@ __global__ __launch_bounds__(CH_NT) void mlp_chain_fwd_kernel(const MlpFwdArgs A
         ch_bias<NRB>(acc, biasl + N::f32_b_trunk, h);
         ch_phase<N, NS, DT, HAS_ALPHA, NRB, SC::GT, N::KKX / SC::GT, B_PEX, true, 0, KKH>(cx, acc, xin, peimg, row);
         ch_convert<NS, DT, true, NRB, KKH, stash_on>(acc, xin, mrow(0), lane);
-        PROF_T(t_trunk);
         // ---- layers 1 .. NL-1 ----
 #pragma unroll 1
         for (int l = 1; l < NL; ++l) {
             ch_bias<NRB>(acc, biasl + N::f32_b_trunk + l * HW, h);
             if (l == N::SKIP)
                 ch_phase<N, NS, DT, HAS_ALPHA, NRB, SC::GT, N::KKX / SC::GT, B_PEX, true, 0, KKH>(cx, acc, xin, peimg, row);
-            PROF_T(t_ph);
             ch_phase<N, NS, DT, HAS_ALPHA, NRB, SC::GT, KKH / SC::GT, B_REG, true, 0, KKH, SPK, HW>(cx, acc, xin, peimg, row, tile_w,
                                                                                  A.h0 + (l - 1) * A.h_stride + wpt * HW, A.plane_h);
-            PROF_ADD(3, t_ph);
-            PROF_T(t_cv);
             ch_convert<NS, DT, true, NRB, KKH, stash_on>(acc, xin, mrow(l), lane);
-            PROF_ADD(4, t_cv);
         }
-        PROF_ADD(2, t_trunk);
         // ---- feature head (no activation) and alpha head, both on h_{NL-1} ----
         ch_bias<NRB>(acc, biasl + N::f32_b_feat, h);
         ch_phase<N, NS, DT, HAS_ALPHA, NRB, SC::GT, KKH / SC::GT, B_REG, false, 0, KKH, SPK, HW>(cx, acc, xin, peimg, row, tile_w,
@@ -637,12 +581,6 @@ __global__ __launch_bounds__(CH_NT) void mlp_chain_fwd_kernel(const MlpFwdArgs A
             *reinterpret_cast<float4*>(A.raw + gpt * 4) = o;
         }
     }
-#ifdef LUSH_PROF
-    if (blockIdx.x == 0 && tid == 0) {
-        prof[0] = __builtin_amdgcn_s_memtime() - t_kernel;
-        for (int i = 0; i < 8; ++i) lush_prof[i] = prof[i];
-    }
-#endif
     wait_vm<0>();          // the look-ahead DMAs of the non-existent next tile must land before the LDS is released
 }
 
@@ -687,13 +625,6 @@ struct HfSched {
 // acc[rb][q] = bias[32 rb + 16 (q>>3) + 8 h + (q&7)] straight from global memory (L2-resident fp32 block)
 template <int NB>
 __device__ __forceinline__ void ch_bias_g(f32x16 (&acc)[NB], const float* __restrict__ b, int h) {
-#ifdef LUSH_ABL_NOBIAS     // timing ablation only (wrong results): no bias loads
-#pragma unroll
-    for (int rb = 0; rb < NB; ++rb)
-#pragma unroll
-        for (int q = 0; q < 16; ++q) acc[rb][q] = 0.f;
-    return;
-#endif
 #pragma unroll
     for (int rb = 0; rb < NB; ++rb) {
         const f32x4* p = reinterpret_cast<const f32x4*>(b + rb * 32 + 8 * h);
@@ -744,11 +675,7 @@ __global__ __launch_bounds__(CH_NT, 2) void mlp_chain_fwd_half_kernel(const MlpF
 #pragma unroll
     for (int j = 0; j < SC::S; ++j) ch_issue<SC::TRUNK_PIECES, SC::SLOT>(cx, (unsigned)j * SC::SLOT, j);
 
-#ifdef LUSH_ABL_NOMASK      // timing ablation only: no ReLU-decision words
-    constexpr bool stash_on = false;
-#else
     constexpr bool stash_on = SPK > 0;
-#endif
     const int row = w * 32 + n;
     char* tile_w = stage + w * 4096;
     // Inference (no stash): the transposition tiles are free, so the fp32 bias block lives there and the per-layer
@@ -763,12 +690,9 @@ __global__ __launch_bounds__(CH_NT, 2) void mlp_chain_fwd_half_kernel(const MlpF
         const long long pt0 = (long long)tile * CH_MT;
         const long long gpt = pt0 + row;
         const long long wpt = pt0 + w * 32;
-#ifndef LUSH_ABL_NOPE    // timing ablation only (wrong results)
         pe_tile<NS, CH_MT, CH_NT, DT>(peimg, PE_PLANE, PE_ROW * 2, A.rays, A.z, A.S, P, pt0, tid, A.live_idx);
-#endif
         wait_vm<0>();      // first tile: the prologue DMAs; later tiles: already published by the last mid-step
         lds_barrier();
-#ifndef LUSH_ABL_NOPECOPY
         if (SPK > 0) {
             for (int i = tid; i < CH_MT * 12; i += CH_NT) {
                 const int c = i % 12, pt = i / 12;
@@ -776,7 +700,6 @@ __global__ __launch_bounds__(CH_NT, 2) void mlp_chain_fwd_half_kernel(const MlpF
                 *reinterpret_cast<uint4*>(A.pe + (pt0 + pt) * PE_ROW + c * 8) = v;
             }
         }
-#endif
         cx.trunk_pos = 0;
         {
             unsigned long long gb = (unsigned long long)cx.gbase;
@@ -1026,10 +949,6 @@ __global__ __launch_bounds__(CH_NT) void mlp_chain_bwd_kernel(const MlpBwdArgs A
 #pragma unroll
             for (int j = 0; j < 8; ++j) xin[kb][p][j] = (__bf16)0.f;
 
-#ifdef LUSH_PROF
-    unsigned long long prof[8] = {0, 0, 0, 0, 0, 0, 0, 0};
-    const unsigned long long t_kernel = __builtin_amdgcn_s_memtime();
-#endif
     for (int tile = blockIdx.x; tile < n_tiles; tile += gridDim.x) {
         const long long pt0 = (long long)tile * CH_MT;
         const long long gpt = pt0 + row;
@@ -1102,16 +1021,11 @@ __global__ __launch_bounds__(CH_NT) void mlp_chain_bwd_kernel(const MlpBwdArgs A
             if (l == N::SKIP)     // gamma(x) rows of the skip layer's input
                 ChPhase<SC, NS, DT, 2, SC::G_X, SC::NP_X, B_REG, true, 0, KKH, 0, 1>::run(cx, apx, xin, nullptr, row, nullptr, nullptr, 0);
             bw_zero<NRB>(acc);
-            PROF_T(t_ph);
             ChPhase<SC, NS, DT, NRB, SC::GT, SC::NP_H, B_REG, true, 0, KKH, NS, HW>::run(cx, acc, xin, nullptr, row, tile_w,
                                                                                       A.dz0 + l * A.dz_stride + wpt * HW, A.plane_h);
-            PROF_ADD(3, t_ph);
-            PROF_T(t_cv);
             bw_convert<NS, true, NRB, KKH, DT>(acc, xin, mw);
             asm volatile("" ::"v"(xin[0][0]), "v"(xin[KKH - 1][0]));
-            PROF_ADD(4, t_cv);
         }
-        PROF_T(t_pe);
         // ---- layer 0: d gamma(x) += W_0^T dZ_0 ----
         ChPhase<SC, NS, DT, 2, SC::G_X, SC::NP_X, B_REG, true, 0, KKH, 0, 1>::run(cx, apx, xin, nullptr, row, nullptr, nullptr, 0);
         bw_stash_all<NS, KKH, KKH, HW>(xin, tile_w, A.dz0 + wpt * HW, A.plane_h, lane);
@@ -1164,14 +1078,7 @@ __global__ __launch_bounds__(CH_NT) void mlp_chain_bwd_kernel(const MlpBwdArgs A
             const long long gp = pt0 + pt;
             if (gp < P) A.dpts[gp * 8 + (c < 3 ? c : c + 1)] = sum * ginv;
         }
-        PROF_ADD(1, t_pe);
     }
-#ifdef LUSH_PROF
-    if (blockIdx.x == 0 && tid == 0) {
-        prof[0] = __builtin_amdgcn_s_memtime() - t_kernel;
-        for (int i = 0; i < 8; ++i) lush_prof[i] = prof[i];
-    }
-#endif
     wait_vm<0>();
 }
 
@@ -1483,14 +1390,6 @@ static int launch_chain_k(const MlpFwdArgs& a, int variant, hipStream_t s) {
     }
     return set_error("launch_mlp_chain_fwd: bad stash plane count");
 }
-
-#ifdef LUSH_PROF
-extern "C" int lush_debug_prof(unsigned long long* out) {
-    LUSH_HIP(hipDeviceSynchronize());
-    LUSH_HIP(hipMemcpyFromSymbol(out, HIP_SYMBOL(lush_prof), sizeof(unsigned long long) * 8));
-    return 0;
-}
-#endif
 
 // planes 1, 2 and the fp16 code run on the chain kernel (128-point tiles); 3 planes keep mlp_fwd_kernel.
 bool mlp_fwd_chain_enabled(int planes) { return planes == 1 || planes == 2 || planes == PLANES_F16; }

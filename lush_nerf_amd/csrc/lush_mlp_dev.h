@@ -145,8 +145,8 @@ __device__ __forceinline__ void dma16s(const void* sbase /* uniform */, unsigned
 }
 
 // The same for bytes that ONE workgroup reads ONCE (the weight-gradient kernel's stash stream): non-temporal policy
-// (MI355X_MICROARCH.md, row nt-weights: issued -> landed -18 %).  Same-box A/B, fine pass, alternating processes (round 5,
-// tools/ab_r05.sh): 4.093 / 4.098 ms against 4.189 / 4.196 ms with the default policy (-2.3 %).  The weight streams of the
+// (MI355X_MICROARCH.md, row nt-weights: issued -> landed -18 %).  Same-box A/B, fine pass, alternating processes (round 5):
+// 4.093 / 4.098 ms against 4.189 / 4.196 ms with the default policy (-2.3 %).  The weight streams of the
 // forward / chain kernels keep the default policy: every CU re-reads them from L2.
 __device__ __forceinline__ void dma16s_stream(const void* sbase /* uniform */, unsigned voff, unsigned lds_base /* uniform */) {
     unsigned keep;

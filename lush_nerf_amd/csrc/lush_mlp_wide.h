@@ -50,9 +50,6 @@ __device__ __forceinline__ void wd_wait_vm() { asm volatile("s_waitcnt vmcnt(%0)
 
 
 struct WdCtx {
-#ifdef LUSH_PROF
-    unsigned long long prof[16];
-#endif
     const char* ring;      // LDS ring (generic pointer, fragment reads)
     unsigned ring_lds;     // its LDS byte address (DMA destination)
     const char* gbase;     // stream base (wave-uniform)

@@ -41,14 +41,6 @@ constexpr int WD_WRAP = NetNerf::fwd4_len / 8;      // stream positions per tile
 static_assert(NetNerf::fwd4_len % 8 == 0, "the quarter-row stream is whole positions");
 
 LUSH_CLOCK_DECL(lush_clock_wide_fwd)
-#ifdef LUSH_PROF   // developer build: cycle counts (s_memtime) of block 0 / wave 0, read back through lush_debug_prof_wide
-__device__ unsigned long long lush_prof_wide[16];
-#define WPROF_T(var) const unsigned long long var = __builtin_amdgcn_s_memtime()
-#define WPROF_ADD(slot, t0) cx.prof[slot] += __builtin_amdgcn_s_memtime() - (t0)
-#else
-#define WPROF_T(var)
-#define WPROF_ADD(slot, t0)
-#endif
 
 // Per-pass runtime parameters (wave-uniform unless noted)
 struct WdRt {
@@ -265,9 +257,7 @@ struct WdPass {
             cx.fetch_off = cx.fetch_off + WD_SLOT == (unsigned)WD_WRAP * WD_SLOT ? 0u : cx.fetch_off + WD_SLOT;
             cx.slot_off = cx.slot_off + WD_SLOT == (unsigned)WD_S * WD_SLOT ? 0u : cx.slot_off + WD_SLOT;
         } else if constexpr (M == 8) {
-#ifndef LUSH_ABL_NODMA
             wd_dma_pair(cx.gbase + r.dma_off, cx.gbase + r.dma_off + 4096u, cx.voff, r.dma_dst, r.dma_dst + 4096u);
-#endif
             cr.a0[0] = *reinterpret_cast<const bf16x8*>(rd_next + cx.lane * 16);
         } else if constexpr (M >= 9 && M <= 11) {
             cr.a0[M - 8] = *reinterpret_cast<const bf16x8*>(rd_next + (M - 8) * 1024 + cx.lane * 16);
@@ -292,9 +282,6 @@ struct WdPass {
 
     template <int G>
     static __device__ __forceinline__ void pending(f32x16 (&pend)[2][2], u32x4 (&xout)[2][16], Regs& r, const WdRt& rt, int lane, float (&alpha)[2]) {
-#ifdef LUSH_ABL_NOCONV      // timing ablation only (wrong results): the MFMA + fragment / DMA skeleton alone
-        return;
-#endif
         if constexpr (CK == WC_ACT) {
             wd_unroll<SC.first[G], SC.first[G + 1]>([&](auto kc) __attribute__((always_inline)) { item<decltype(kc)::value>(pend, xout, r, rt, lane); });
         } else if constexpr (CK == WC_ALPHA) {
@@ -327,22 +314,11 @@ struct WdPass {
 
     template <int JOB, int I4>
     static __device__ __forceinline__ void stash_store(const WdCarry& cr, const WdRt& rt) {
-        constexpr int c = JOB / 4, j = JOB % 4;      // uniform row-block base + ONE per-lane offset
-#ifndef LUSH_ABL_NOSTORE
-#ifdef LUSH_PLAIN_STASH      // developer A/B: cached stores (tools/micro/mall_probe.hip: a pure write stream is faster with them)
-        *reinterpret_cast<u32x4*>(rt.srows + ((c * 32 + 8 * I4) * LD + j * 64) * 2 + rt.srow_off) = cr.sb[I4 % WD_SB];
-#else
+        constexpr int c = JOB / 4, j = JOB % 4;      // uniform row-block base + ONE per-lane offset; non-temporal: write-once stream
         __builtin_nontemporal_store(cr.sb[I4 % WD_SB], reinterpret_cast<u32x4*>(rt.srows + ((c * 32 + 8 * I4) * LD + j * 64) * 2 + rt.srow_off));
-#endif
-#else
-        asm volatile("" ::"v"(cr.sb[I4 % WD_SB]));
-#endif
     }
     template <int G>
     static __device__ __forceinline__ void stash(const u32x4 (&xin)[2][16], WdCarry& cr, const WdRt& rt, int lane) {
-#ifdef LUSH_ABL_NOSTASH      // timing ablation only (wrong results): no LDS transposition, no row stores
-        return;
-#endif
         constexpr int P = 4 * PQ + G / 16, m = G % 16;
         if constexpr (st_store(G)) stash_store<st_store_job(G), st_store_row(G)>(cr, rt);
         if constexpr (st_write(G)) {
@@ -390,21 +366,8 @@ struct WdPass {
         // mid-step: my pieces of position +1 have landed (the DMAs of +2 .. +S-1 and the stores issued since are younger);
         // after the barrier everyone's have, and nobody reads this position's slot any more
         constexpr int younger = 2 * (WD_S - 2) + (MAIN ? stores_in(16 * (I + 1 - WD_S) + 8, 16 * I + 8) : 0);
-        WPROF_T(t_w0);
-#ifndef LUSH_ABL_NOVMWAIT
         wd_wait_vm<(younger < 63 ? younger : 63)>();
-#endif
-        WPROF_T(t_w1);
-#ifndef LUSH_ABL_NOBAR
         lds_barrier();
-#else
-        asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
-#endif
-#ifdef LUSH_PROF
-        cx.prof[5] += t_w1 - t_w0;
-        cx.prof[6] += __builtin_amdgcn_s_memtime() - t_w1;
-        cx.prof[7] += 1;
-#endif
         const char* rd_next = cx.ring + cx.slot_off;        // (slot_off already names the next slot: gap 5)
         __builtin_amdgcn_sched_barrier(0);
         wd_unroll<8, 16>([&](auto mc) __attribute__((always_inline)) {
@@ -535,10 +498,6 @@ __global__ __launch_bounds__(WD_NT) void mlp_wide_fwd_kernel(const MlpFwdArgs A)
     cx.w = w;
     cx.lane = lane;
     cx.voff = (unsigned)lane * 16u + (unsigned)w * 1024u;
-#ifdef LUSH_PROF
-    for (int i = 0; i < 16; ++i) cx.prof[i] = 0;
-    const unsigned long long t_kernel = __builtin_amdgcn_s_memtime();
-#endif
 #pragma unroll
     for (int j = 0; j < WD_S; ++j)
         wd_dma_pair(cx.gbase + (unsigned)j * WD_SLOT, cx.gbase + (unsigned)j * WD_SLOT + 4096u, cx.voff, cx.dma_base + (unsigned)j * WD_SLOT, cx.dma_base + (unsigned)j * WD_SLOT + 4096u);
@@ -563,10 +522,7 @@ __global__ __launch_bounds__(WD_NT) void mlp_wide_fwd_kernel(const MlpFwdArgs A)
     for (int tile = blockIdx.x; tile < n_tiles; tile += gridDim.x) {
         const long long pt0 = (long long)tile * WD_MT;
         const long long wpt = pt0 + row0;
-        WPROF_T(t_tile);
-#ifndef LUSH_ABL_NOPE
         wd_pe_tile(peimg, A.rays, A.z, A.S, P, pt0, tid, (SPK > 0 && !A.pe_rows) ? A.xd : nullptr, A.live_idx);
-#endif
         // my pieces of the tile's first position have landed.  First tile: the prologue issued S positions, S-1 are younger.
         // Later tiles: that DMA left S positions ago, in the views layer's second quarter; younger are the DMAs of S-1
         // positions and AT LEAST the 16 stash stores of the views hidden + the raw store (an undercount is safe) -- a full
@@ -605,8 +561,6 @@ __global__ __launch_bounds__(WD_NT) void mlp_wide_fwd_kernel(const MlpFwdArgs A)
         wd_bias(accA, btr, h, 2);
         wd_bias(accB, btr + 64, h, 2);
 
-        WPROF_ADD(1, t_tile);
-        WPROF_T(t_l0);
         // ---- layer 0: gamma(x) from the PE image, four quarter passes of one position ----
         rt.clamp = 0u;
         WdPass<2, 1, WB_PEX, 0, WB_NONE, WC_NONE, 2, 0, MASK, 2, 16, 0, false, HW>::run(cx, accA, accB, B0, B0, a0, peimg, row0, rt, alpha);
@@ -623,11 +577,7 @@ __global__ __launch_bounds__(WD_NT) void mlp_wide_fwd_kernel(const MlpFwdArgs A)
             const bool feat = l == NL;
             const float* bl = btr + l * HW;                         // (the feature biases follow the trunk biases)
             rt.pre_on = l == N::SKIP;
-#ifdef LUSH_ABL_H0      // timing ablation only (wrong results): the h_0 rows go to one tile's worth of rows per workgroup (no HBM traffic)
-            rt.srows = reinterpret_cast<char*>(A.h0 + (long long)(l - 1) * A.h_stride + (l == 1 ? (long long)blockIdx.x * WD_MT + (wpt % WD_MT) : wpt) * HW);
-#else
             rt.srows = reinterpret_cast<char*>(A.h0 + (long long)(l - 1) * A.h_stride + wpt * HW);
-#endif
             // pass 0: set A accumulates rows 0..63; set B (last quarter of the previous layer) -> xin k-blocks 12..15
             rt.clamp = 0u; mset(l - 1, 6, false); rt.nextbias = bl + 64;
             WdPass<2, 4, WB_REG, 0, WB_PEX, WC_ACT, 2, 12, MASK, 2, 48, 0, (SPK > 0), HW>::run(cx, accA, accB, xin, xin, a0, peimg, row0, rt, alpha);
@@ -639,15 +589,11 @@ __global__ __launch_bounds__(WD_NT) void mlp_wide_fwd_kernel(const MlpFwdArgs A)
             mset(l, 4, feat); rt.nextbias = feat ? biasl + N::f32_b_alpha : bl + HW;
             WdPass<2, 4, WB_REG, 0, WB_PEX, WC_ACT, 2, 8, MASK, 2, 60, 3, (SPK > 0), HW>::run(cx, accB, accA, xin, xout, a0, peimg, row0, rt, alpha);
         };
-        WPROF_ADD(2, t_l0);
-        WPROF_T(t_trunk);
 #pragma unroll 1
         for (int l2 = 0; l2 < NL / 2; ++l2) {
             layer(1 + 2 * l2, B0, B1);
             layer(2 + 2 * l2, B1, B0);
         }
-        WPROF_ADD(3, t_trunk);
-        WPROF_T(t_tail);
         // now: B1 = h_{NL-1}, B0 = feature k-blocks 0..11; set B holds the feature layer's last quarter, set A the alpha bias
         rt.pre_on = false;
         // ---- alpha head on h_{NL-1} (1 row block, 2 positions); set B -> feature k-blocks 12..15 ----
@@ -670,7 +616,6 @@ __global__ __launch_bounds__(WD_NT) void mlp_wide_fwd_kernel(const MlpFwdArgs A)
         }
         if constexpr (SPK > 0) {    // views hidden -> stash rows [point][HV]
             char* hvrows = reinterpret_cast<char*>(A.hv + wpt * HV);
-#ifndef LUSH_WD_DIRECT_STASH
 #pragma unroll
             for (int c = 0; c < 2; ++c)
 #pragma unroll
@@ -685,14 +630,6 @@ __global__ __launch_bounds__(WD_NT) void mlp_wide_fwd_kernel(const MlpFwdArgs A)
                         __builtin_nontemporal_store(v, reinterpret_cast<u32x4*>(hvrows + ((c * 32 + 8 * i) * HV + j * 64) * 2 + (unsigned)(((lane >> 3) * HV + (lane & 7) * 8) * 2)));
                     }
                 }
-#else
-#pragma unroll
-            for (int c = 0; c < 2; ++c) {
-                const unsigned off = (unsigned)(((c * 32 + n) * HV + h * 8) * 2);
-#pragma unroll
-                for (int kb = 0; kb < N::KKV; ++kb) __builtin_nontemporal_store(B1[c][kb], reinterpret_cast<u32x4*>(hvrows + off + kb * 32));
-            }
-#endif
         }
         // ---- rgb head (1 row block, 1 position) ----
         WdPass<1, 1, WB_REG, 0, WB_NONE, WC_NONE, 2, 0, MASK, 2, 16, 0, false, HW>::run(cx, accB, accA, B1, B1, a0, peimg, row0, rt, alpha);
@@ -710,17 +647,7 @@ __global__ __launch_bounds__(WD_NT) void mlp_wide_fwd_kernel(const MlpFwdArgs A)
                 }
             }
         }
-        WPROF_ADD(4, t_tail);
-#ifdef LUSH_PROF
-        cx.prof[8] += 1;
-#endif
     }
-#ifdef LUSH_PROF
-    if (blockIdx.x == 0 && tid == 0) {
-        cx.prof[0] = __builtin_amdgcn_s_memtime() - t_kernel;
-        for (int i = 0; i < 16; ++i) lush_prof_wide[i] = cx.prof[i];
-    }
-#endif
     wd_wait_vm<0>();          // the look-ahead DMAs of the non-existent next tile must land before the LDS is released
     LUSH_CLOCK_STAMP(lush_clock_wide_fwd, 1);
 }
@@ -748,14 +675,6 @@ static int launch_wide_sp(const MlpFwdArgs& a, hipStream_t s) {
     LUSH_HIP(hipGetLastError());
     return 0;
 }
-
-#ifdef LUSH_PROF
-extern "C" int lush_debug_prof_wide(unsigned long long* out) {
-    LUSH_HIP(hipDeviceSynchronize());
-    LUSH_HIP(hipMemcpyFromSymbol(out, HIP_SYMBOL(lush_prof_wide), sizeof(unsigned long long) * 16));
-    return 0;
-}
-#endif
 
 // One fp16 plane, the 8x256 net: a.stash_planes 0 (inference) or 1.
 int launch_mlp_wide_fwd(const MlpFwdArgs& a, hipStream_t s) {

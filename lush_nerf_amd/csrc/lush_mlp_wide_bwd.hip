@@ -24,14 +24,6 @@ namespace lush {
 
 constexpr int WB_WRAP = NetNerf::bwd4_len / 8;      // stream positions per tile
 LUSH_CLOCK_DECL(lush_clock_wide_bwd)
-#ifdef LUSH_PROF   // developer build: cycle counts (s_memtime) of block 0 / wave 0, read back through lush_debug_prof_wbwd
-__device__ unsigned long long lush_prof_wbwd[16];
-#define BPROF_T(var) const unsigned long long var = __builtin_amdgcn_s_memtime()
-#define BPROF_ADD(slot, t0) cx.prof[slot] += __builtin_amdgcn_s_memtime() - (t0)
-#else
-#define BPROF_T(var)
-#define BPROF_ADD(slot, t0)
-#endif
 static_assert(NetNerf::bwd4_len % 8 == 0, "the transposed quarter-row stream is whole positions");
 constexpr int WB_DPE_LD = 104;                      // 16-bit elements per point in the d(gamma) image (96 used; rows stay 16-byte aligned;
                                                     // 52 dwords: 16 rows at one chunk fall on 16 disjoint bank quads)
@@ -246,13 +238,7 @@ struct WbPass {
         constexpr int b = it.b, t = it.t, c = b % 2, rbl = b / 2;
         if constexpr (it.kind == WI_L) {
             unsigned a;
-#ifdef LUSH_ABL_LUTFREE      // timing ablation only (wrong masks): every lane of a 16-lane group reads its own bank quad -- what the table reads' bank
-            // conflicts cost.  Entry 17 x (lane & 15) = 0x00, 0x11 .. 0xFF: bank quad lane & 15, and HALF of the decisions set on average,
-            // as in the real masks (entries 0 .. 15 would zero three quarters of dZ: a lighter operand stream, a higher clock)
-            asm volatile("v_mbcnt_lo_u32_b32 %0, -1, 0\n\tv_and_b32 %0, 15, %0\n\tv_mul_u32_u24 %0, 17, %0" : "=v"(a) : "v"(r.ct.w[b]));
-#else
             asm volatile("v_bfe_u32 %0, %1, %2, 8" : "=v"(a) : "v"(r.ct.w[b]), "n"(8 * t));
-#endif
             r.ct.Y[(2 * b + t) % 2] = *reinterpret_cast<const u32x4*>(rt.lut + a * 16);
         } else if constexpr (it.kind == WI_P || it.kind == WI_ID) {
             constexpr int i = it.i;
@@ -285,9 +271,6 @@ struct WbPass {
 
     template <int G>
     static __device__ __forceinline__ void pending(f32x16 (&pend)[2][2], u32x4 (&xout)[2][16], Regs& r, const WbRt& rt) {
-#ifdef LUSH_ABL_NOCONV      // timing ablation only (wrong results)
-        return;
-#endif
         wd_unroll<SC.first[G], SC.first[G + 1]>([&](auto kc) __attribute__((always_inline)) { item<decltype(kc)::value>(pend, xout, r, rt); });
     }
 
@@ -297,23 +280,12 @@ struct WbPass {
     template <int JOB, int I4>
     static __device__ __forceinline__ void stash_store(const WdCarry& cr, const WbRt& rt) {
         constexpr int c = JOB / 4, j = JOB % 4;
-#ifndef LUSH_ABL_NOSTORE
         // (s_nop 1: a store of more than 8 bytes reads its data registers for two more cycles -- the hazard the compiler covers for its
         // own stores; without it the conversion's VALU code, which re-uses the row's registers at once, reached memory in some lanes)
-#ifdef LUSH_PLAIN_STASH      // developer A/B: cached stores
-        asm volatile("global_store_dwordx4 %0, %1, %2\n\ts_nop 1" ::"v"(rt.srow_off), "v"(cr.sb[I4 % WB_SB]), "s"(rt.srows + ((c * 32 + 8 * I4) * LD + j * 64) * 2) : "memory");
-#else
         asm volatile("global_store_dwordx4 %0, %1, %2 nt\n\ts_nop 1" ::"v"(rt.srow_off), "v"(cr.sb[I4 % WB_SB]), "s"(rt.srows + ((c * 32 + 8 * I4) * LD + j * 64) * 2) : "memory");
-#endif
-#else
-        asm volatile("" ::"v"(cr.sb[I4 % WB_SB]));
-#endif
     }
     template <int G>
     static __device__ __forceinline__ void stash(const u32x4 (&xin)[2][16], WdCarry& cr, const WbRt& rt, int lane) {
-#ifdef LUSH_ABL_NOSTASH
-        return;
-#endif
         constexpr int P = 4 * PQ + G / 16, m = G % 16;
         if constexpr (st_store(G)) stash_store<st_store_job(G), (m >= 14 ? m - 14 : m + 2)>(cr, rt);
         if constexpr (st_write(G)) {
@@ -357,17 +329,8 @@ struct WbPass {
         // (XP: the pass's first XP positions are among the first S - 1 of a tile: the piece awaited was requested in the previous
         // tile, in front of everything the tile boundary issues)
         constexpr int younger = 2 * (WD_S - 2) + others_in(16 * (I + 1 - WD_S) + 8, 16 * I + 8) + (I < XP ? WB_TILE_OPS : 0);
-        BPROF_T(t_w0);
-#ifndef LUSH_ABL_NOVMWAIT
         wd_wait_vm<(younger < 63 ? younger : 63)>();
-#endif
-        BPROF_T(t_w1);
         lds_barrier();
-#ifdef LUSH_PROF
-        cx.prof[5] += t_w1 - t_w0;
-        cx.prof[6] += __builtin_amdgcn_s_memtime() - t_w1;
-        cx.prof[7] += 1;
-#endif
         const char* rd_next = cx.ring + cx.slot_off;        // (slot_off already names the next slot: gap 5)
         __builtin_amdgcn_sched_barrier(0);
         wd_unroll<8, 16>([&](auto mc) __attribute__((always_inline)) {
@@ -522,15 +485,10 @@ __global__ __launch_bounds__(WD_NT) void mlp_wide_bwd_kernel(const MlpBwdArgs A)
     // rule R5 follows every path and now finds the wait on each of them.)
     if ((int)blockIdx.x < n_tiles) prefetch(blockIdx.x);
     asm volatile("s_waitcnt vmcnt(0)" : "+v"(drn[0]), "+v"(drn[1])::"memory");
-#ifdef LUSH_PROF
-    for (int i = 0; i < 16; ++i) cx.prof[i] = 0;
-    const unsigned long long t_kernel = __builtin_amdgcn_s_memtime();
-#endif
 
     for (int tile = blockIdx.x; tile < n_tiles; tile += gridDim.x) {
         const long long pt0 = (long long)tile * WD_MT;
         const long long wpt = pt0 + row0;
-        BPROF_T(t_tile);
         {   // opaque per tile (keeps the static stream addresses from being hoisted out of the tile loop)
             unsigned long long gb = (unsigned long long)cx.gbase;
             asm volatile("" : "+s"(gb));
@@ -551,11 +509,7 @@ __global__ __launch_bounds__(WD_NT) void mlp_wide_bwd_kernel(const MlpBwdArgs A)
             dr[c].z = in ? drn[c][2] * gscale : 0.f; dr[c].w = in ? drn[c][3] * gscale : 0.f;
             rt.dalpha[c] = dr[c].w;
         }
-        BPROF_ADD(1, t_tile);      // wait for the prefetch
-        BPROF_T(t_bar);
         lds_barrier();         // the first position's pieces of every wave have landed (and wtab, first tile)
-        BPROF_ADD(2, t_bar);
-        BPROF_T(t_pro);
 
         f32x16 accA[2][2], accB[2][2];
         u32x4 B0[2][16], B1[2][16];
@@ -563,7 +517,6 @@ __global__ __launch_bounds__(WD_NT) void mlp_wide_bwd_kernel(const MlpBwdArgs A)
 #pragma unroll
         for (int i = 0; i < 4; ++i) a0.a0[i] = *reinterpret_cast<const bf16x8*>(cx.ring + cx.slot_off + i * 1024 + cx.voff);
 
-#ifndef LUSH_ABL_NOPRO      // timing ablation only (wrong results)
         // ---- dZv = (Wrgb^T d_rgb) * relu'(hv): K = 3, a rank-3 update on the VALU; rows 0..63 -> set A, 64..127 -> set B ----
         {
             auto rank3 = [&](f32x16 (&acc)[2][2], int r0) __attribute__((always_inline)) {
@@ -615,10 +568,7 @@ __global__ __launch_bounds__(WD_NT) void mlp_wide_bwd_kernel(const MlpBwdArgs A)
 #pragma unroll
                 for (int j = 0; j < N::KKV / 4; ++j) stash_now(B1, c, j, rows, LDV);
         }
-#endif
         // ---- d_feature = Wva^T dZv (four quarters of 2 positions); d gamma(d) = Wvb^T dZv (one position, one row block) ----
-        BPROF_ADD(3, t_pro);       // rank-3 update, conversion, dZv rows
-        BPROF_T(t_body);
         if (tile == (int)blockIdx.x) wd_wait_vm<0>();      // (first tile: no previous tile issued what the counts below assume)
         static_assert(WD_S - 1 == 5, "the first S - 1 positions of a tile: VA0, VA1 and the first of VA2");
         WbPass<2, 2, WK_NONE, 0, false, true, 32, 0, false, HW, false, 2>::run(cx, accA, accB, B1, B0, a0, rt);
@@ -688,9 +638,6 @@ __global__ __launch_bounds__(WD_NT) void mlp_wide_bwd_kernel(const MlpBwdArgs A)
         if (wpt + lane < P) point_of(A.rays, A.z, A.S, A.live_idx ? (long long)A.live_idx[wpt + lane] : wpt + lane, px, pd);
         rt.mrd = mrd0 + 6 * 128;                           // h_0: parity 0
         WbPass<2, 4, WK_ACT, 12, false, true, 48, 0, false, HW, false>::run(cx, accA, accB, B0, B0, a0, rt);
-        BPROF_ADD(4, t_body);      // VA .. layer 0
-        BPROF_T(t_epi);
-#ifndef LUSH_ABL_NOEPI      // timing ablation only (wrong results)
 #pragma unroll
         for (int c = 0; c < 2; ++c) {
             dpe_add(accA[c][0], c, 0); dpe_add(accA[c][1], c, 1);
@@ -716,8 +663,6 @@ __global__ __launch_bounds__(WD_NT) void mlp_wide_bwd_kernel(const MlpBwdArgs A)
 #pragma unroll
                 for (int j = 0; j < 4; ++j) stash_now(B0, c, j, rows, HW);
         }
-        BPROF_ADD(9, t_epi);       // image, prefetch, dZ_0 rows
-        BPROF_T(t_enc);
         // ---- through the encoding: d/dx_i = g[i] + sum_k 2^k (cos(2^k x_i) g_sin - sin(2^k x_i) g_cos), one point per thread.
         // The rows of this wave's 64 points were written by this wave alone: LDS operations of a wave execute in order.
         {
@@ -755,18 +700,7 @@ __global__ __launch_bounds__(WD_NT) void mlp_wide_bwd_kernel(const MlpBwdArgs A)
                 o[1] = make_float4(gd[0], gd[1], gd[2], 0.f);
             }
         }
-#endif
-        BPROF_ADD(10, t_enc);
-#ifdef LUSH_PROF
-        cx.prof[8] += 1;
-#endif
     }
-#ifdef LUSH_PROF
-    if (blockIdx.x == 0 && tid == 0) {
-        cx.prof[0] = __builtin_amdgcn_s_memtime() - t_kernel;
-        for (int i = 0; i < 16; ++i) lush_prof_wbwd[i] = cx.prof[i];
-    }
-#endif
     wd_wait_vm<0>();          // the look-ahead DMAs of the non-existent next tile must land before the LDS is released
     LUSH_CLOCK_STAMP(lush_clock_wide_bwd, 1);
 }
@@ -775,13 +709,6 @@ __global__ __launch_bounds__(WD_NT) void mlp_wide_bwd_kernel(const MlpBwdArgs A)
 // host side
 // ---------------------------------------------------------------------------------------------
 LUSH_CLOCK_EXPORT(lush_debug_clock_chain, lush_clock_wide_bwd)
-#ifdef LUSH_PROF
-extern "C" int lush_debug_prof_wbwd(unsigned long long* out) {
-    LUSH_HIP(hipDeviceSynchronize());
-    LUSH_HIP(hipMemcpyFromSymbol(out, HIP_SYMBOL(lush_prof_wbwd), sizeof(unsigned long long) * 16));
-    return 0;
-}
-#endif
 
 int launch_mlp_wide_bwd(const MlpBwdArgs& a, hipStream_t s) {
     using N = NetNerf;

@@ -35,7 +35,7 @@ def needs_build() -> bool:
 
 
 def use_library(path: str):
-    """Developer tools only (tools/*.py: ablation / profiling builds): load() will open `path` instead of the in-tree product."""
+    """Developer tools only (tools/*.py: a build made by tools/build_variant.py, e.g. a parent commit's for a same-box A/B): load() will open `path` instead of the in-tree product."""
     global SO_PATH, _lib
     if _lib is not None:
         raise RuntimeError("lib.use_library: a library is already loaded")
@@ -46,7 +46,7 @@ def build(force: bool = False, verbose: bool = False, extra_flags: Sequence[str]
     """Compile the HIP sources for gfx950 into lush_nerf_amd/liblush_march.so and audit the result (isa_check).
 
     The product build takes nothing from the environment.  `extra_flags` / `out` are for developer builds (tools/build_variant.py:
-    -DLUSH_PROF, the -DLUSH_ABL_* timing ablations) and refuse to write the product's path."""
+    -DLUSH_CLOCK, a tuning default such as -DLUSH_DW_PE_COST=700) and refuse to write the product's path."""
     product = out is None
     if extra_flags and product:
         raise ValueError("lib.build: extra compiler flags need an explicit `out` path (the in-tree product is built without any)")

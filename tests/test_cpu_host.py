@@ -625,3 +625,29 @@ def test_live_point_policy_reads_a_fixed_lag():
     t._live_step = 7
     t._live_poll()
     assert t.live_share == 1.0 and not t._live_snaps
+
+
+def test_kernel_sources_have_one_compile_time_form():
+    """Every preprocessor conditional in the kernel sources and the public header is an include guard, `__cplusplus`, `LUSH_CLOCK`
+    (lush_common.h: three macros, empty in the product) or an `#ifndef X` / `#define X value` default that selects no code.  Timing
+    ablations and profiling counters do not live inside the product kernels (tools/micro/ prototypes)."""
+    import glob
+    csrc = os.path.join(ROOT, "lush_nerf_amd", "csrc")
+    files = sorted(glob.glob(os.path.join(csrc, "*.hip")) + glob.glob(os.path.join(csrc, "*.h"))) + [os.path.join(ROOT, "include", "lush_march.h")]
+    assert len(files) > 10, files
+    bad, seen = [], 0
+    for f in files:
+        lines = open(f).read().split("\n")
+        for k, line in enumerate(lines):
+            m = re.match(r"\s*#\s*(if|ifdef|ifndef|elif)\b(.*)", line)
+            if not m:
+                continue
+            seen += 1
+            kind, cond = m.group(1), re.sub(r"//.*|/\*.*", "", m.group(2)).strip()
+            if kind == "ifdef" and cond in ("__cplusplus", "LUSH_CLOCK"):
+                continue
+            if kind == "ifndef" and re.fullmatch(r"\w+", cond) and k + 1 < len(lines) and re.match(r"\s*#\s*define\s+%s\b" % cond, lines[k + 1]):
+                continue      # an include guard or a tuning default
+            bad.append(f"{os.path.relpath(f, ROOT)}:{k + 1}: {line.strip()}")
+    assert seen >= 10, seen      # (the scan found the conditionals that are allowed: it is reading the right files)
+    assert not bad, "\n".join(bad)

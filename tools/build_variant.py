@@ -1,12 +1,13 @@
 #!/usr/bin/env python3
-"""Developer tool: build a VARIANT of liblush_march.so next to the product (profiling / timing-ablation builds).
+"""Developer tool: build a VARIANT of liblush_march.so next to the product (an in-kernel clock build, a tuning default, a parent
+commit's sources for a same-box A/B).
 
-  python tools/build_variant.py --out build/wide_prof.so --flags=-DLUSH_PROF            (note the "=": the value starts with a dash)
-  python tools/build_variant.py --out build/noconv.so "--flags=-DLUSH_ABL_NOCONV -DX=1" [--no-audit]
+  python tools/build_variant.py --out build/clock.so --flags=-DLUSH_CLOCK               (note the "=": the value starts with a dash)
+  python tools/build_variant.py --out build/pe700.so "--flags=-DLUSH_DW_PE_COST=700 -DLUSH_CLOCK"
 
-The product build (lib.build(), __graft_entry__.build()) takes no flags from anywhere; this is the only way to compile the
--DLUSH_ABL_* branches (wrong results by construction: timing only) and it never writes the product's path.  The ISA audit
-(lush_nerf_amd/isa_check.py) runs on variants too; --no-audit is for ablations that remove the instructions a rule looks at.
+The product build (lib.build(), __graft_entry__.build()) takes no flags from anywhere; this is the only way to pass extra compiler
+flags and it never writes the product's path.  The ISA audit (lush_nerf_amd/isa_check.py) runs on variants too; --no-audit is for
+experiments that remove the instructions a rule looks at.
 Load a variant from a tool with lib.use_library(path) before lib.load() (tools/bench_mlp.py: SO=...).
 """
 import argparse
