@@ -250,12 +250,12 @@ int lush_draws(unsigned long long seed, unsigned long long offset, float* t_rand
  * models/lushnerf.py:234-293).
  * net 0 = NeRF (D=8, W=256, skip after layer 4), net 1 = NeRF_Noise (D=4, W=128).
  * planes = bf16 planes per operand: 1 plain bf16, 2 parity mode (~2^-17), 3 ~fp32. */
-typedef struct {
+typedef struct lush_mlp_params {
     const float* w[8];
     const float* b[8];
     const float *w_feat, *b_feat, *w_alpha, *b_alpha, *w_views, *b_views, *w_rgb, *b_rgb;
 } lush_mlp_params;
-typedef struct {
+typedef struct lush_mlp_grads {
     float* w[8];
     float* b[8];
     float *w_feat, *b_feat, *w_alpha, *b_alpha, *w_views, *b_views, *w_rgb, *b_rgb;
@@ -464,6 +464,13 @@ int lush_adam_state_multi(float* param, const float* grad, float* m, float* v, l
 
 /* Test hooks (tests/ only): raw access to a stash array for layer-wise parity. */
 int lush_debug_stash_layout(int net, int planes, long long P, long long* offsets /* host, 16 entries */);
+/* How a backward over P points cuts up its grouped weight-gradient launch (one and two backward planes) on a device of n_cu CUs:
+ * the job table with dummy addresses and the launch plan of it.  Host only: no device, no launch.
+ *   plan[0..6] = jobs n, form (DwGroup::per_job 0..3), padded points, points per slice, grid x, grid y, 1 if the chunk cursors are used;
+ *   plan[7 + 6 i ..] for job i < n (at most 12) = output rows, input columns, columns of the second block, its encoding mode,
+ *   points per slice of this job (form 2), first workgroup (forms 2, 3);  plan[79] = first[n];  unused entries are -1.
+ * A live launch (live != 0) is refused where lush_mlp_bwd_weights_live refuses it. */
+int lush_debug_dw_plan(int net, int planes_f, int planes_b, long long P, int variant, int live, int n_cu, long long* plan /* host, 80 entries */);
 
 #ifdef __cplusplus
 }

@@ -4,6 +4,9 @@
 #include <atomic>
 #include "lush_mlp.h"
 
+struct lush_mlp_params;      // include/lush_march.h
+struct lush_mlp_grads;
+
 namespace lush {
 
 int set_error(const char* msg);                 // stores a thread-local message, returns -1
@@ -43,13 +46,11 @@ inline int kernel_lds_once(KernelOnce& once, int dev, const void* kernel, size_t
 }
 
 // lush_abi.hip: the halves of lush_mlp_bwd for a caller whose lush_composite_bwd prepared the dstash header (lush_march_bwd)
-// (prm / g are const lush_mlp_params* / const lush_mlp_grads*, stream a hipStream_t: passed untyped so that this header does not
-// depend on include/lush_march.h)
 int mlp_bwd_chain_prepared(int net, int planes_f, int planes_b, const float* rays, const float* z, int R, int S,
-                           const void* packed_b, const void* prm, const float* draw, const void* stash,
-                           void* dstash, float* dpts, int variant, void* stream, const int* live_idx = nullptr, const int* live_cnt = nullptr);
-int mlp_bwd_weights_prepared(int net, int planes_f, int planes_b, int R, int S, const void* prm, const float* draw,
-                             const void* stash, void* dstash, const void* g, int variant, void* stream, const int* live_cnt = nullptr);
+                           const void* packed_b, const lush_mlp_params* prm, const float* draw, const void* stash,
+                           void* dstash, float* dpts, int variant, hipStream_t stream, const int* live_idx = nullptr, const int* live_cnt = nullptr);
+int mlp_bwd_weights_prepared(int net, int planes_f, int planes_b, int R, int S, const lush_mlp_params* prm, const float* draw,
+                             const void* stash, void* dstash, const lush_mlp_grads* g, int variant, hipStream_t stream, const int* live_cnt = nullptr);
 bool mlp_live_kernels(int net, int planes_f, int planes_b, int variant);      // the kernels of this mode take live-point launches
 bool mlp_dstash_header(int net, int planes_b, long long P, void* dstash, float** scale4, float** zero_buf, long long* zero_n);
 

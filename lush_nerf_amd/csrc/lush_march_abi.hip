@@ -227,17 +227,17 @@ int lush_march_bwd(const lush_march_cfg* cfg, const float* rays, const lush_mlp_
             const void* pkf = pk_fwd;            // forward fragments: the caller's buffer or the forward call's copy in the workspace
             rc = lush_mlp_fwd_live(0, pf, sc, rays, z, R, Sp, pkf, prm, w + stashoff, lidx, lcnt, var, st);
             if (rc) return rc;
-            rc = mlp_bwd_chain_prepared(0, sc, pb, rays, z, R, Sp, pk, prm, draw_c, w + stashoff, x.dstash, x.dpts, var, st, lidx, lcnt);
+            rc = mlp_bwd_chain_prepared(0, sc, pb, rays, z, R, Sp, pk, prm, draw_c, w + stashoff, x.dstash, x.dpts, var, (hipStream_t)st, lidx, lcnt);
             if (rc) return rc;
             return lush_ray_grad_reduce_live(x.dpts, z, lidx, (const int*)(w + L.ray_start), R, drays, st);
         }
-        rc = mlp_bwd_chain_prepared(0, sc, pb, rays, z, R, Sp, pk, prm, x.draw, w + stashoff, x.dstash, x.dpts, var, st);
+        rc = mlp_bwd_chain_prepared(0, sc, pb, rays, z, R, Sp, pk, prm, x.draw, w + stashoff, x.dstash, x.dpts, var, (hipStream_t)st);
         if (rc) return rc;
         return lush_ray_grad_reduce(x.dpts, z, R, Sp, drays, st);
     };
     auto weights = [&](const lush_mlp_params* prm, const lush_mlp_grads* gr, size_t stashoff, int Sp, int slot) -> int {
-        if (L.live) return mlp_bwd_weights_prepared(0, sc, pb, R, Sp, prm, (const float*)(w + L.draw_c), w + stashoff, x.dstash, gr, var, st, (const int*)(w + L.live_cnt) + 2 * slot);
-        return mlp_bwd_weights_prepared(0, sc, pb, R, Sp, prm, x.draw, w + stashoff, x.dstash, gr, var, st);
+        if (L.live) return mlp_bwd_weights_prepared(0, sc, pb, R, Sp, prm, (const float*)(w + L.draw_c), w + stashoff, x.dstash, gr, var, (hipStream_t)st, (const int*)(w + L.live_cnt) + 2 * slot);
+        return mlp_bwd_weights_prepared(0, sc, pb, R, Sp, prm, x.draw, w + stashoff, x.dstash, gr, var, (hipStream_t)st);
     };
     const bool any_main = g->rgb || g->depth || g->acc;
     const bool any_c = two ? (g->rgb0 || g->depth0 || g->acc0) : any_main;

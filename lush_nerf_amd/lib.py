@@ -215,6 +215,7 @@ _SIGS = {
     "lush_adam_multi": ([_p, _p, _p, _p, _ll, _ll, _ll, _i, _f, _f, _f, _f, _p, _f, _p], _i),
     "lush_adam_state_multi": ([_p, _p, _p, _p, _ll, _ll, _ll, _p, _i, _f, _f, _f, _f, _p], _i),
     "lush_debug_stash_layout": ([_i, _i, _ll, C.POINTER(_ll)], _i),
+    "lush_debug_dw_plan": ([_i, _i, _i, _ll, _i, _i, _i, C.POINTER(_ll)], _i),
 }
 EXPORTS = ["lush_last_error"] + list(_SIGS)
 ABI_VERSION = 10

@@ -651,3 +651,46 @@ def test_kernel_sources_have_one_compile_time_form():
             bad.append(f"{os.path.relpath(f, ROOT)}:{k + 1}: {line.strip()}")
     assert seen >= 10, seen      # (the scan found the conditionals that are allowed: it is reading the right files)
     assert not bad, "\n".join(bad)
+
+
+def test_weight_gradient_launch_plan_is_pinned():
+    """How a backward cuts up its grouped weight-gradient launch (plan_dw_group in lush_abi.hip, a third of the headline step) decided
+    on the host from the job table, the padded point count, live or dense, the variant word and the CU count: lush_debug_dw_plan
+    returns it without a device.  Every word equals tests/dw_plan_expected.json, recorded from the dispatch code as it stood before
+    it was taken apart (a scratch hook in front of its launch_dw_group call); null there = the call is refused (a live launch of the
+    noise net or with an older-kernel variant bit).  Plus what holds without a table."""
+    import itertools
+    import json
+    l = lib.load()
+    want = json.load(open(os.path.join(ROOT, "tests", "dw_plan_expected.json")))
+    MAX_PTS = 262144                                      # LUSH_DW_PERJOB_MAX_PTS
+    variants = (0, lib.VARIANT_HEAD_KERNEL, lib.VARIANT_PE_ROWS, lib.VARIANT_DW_SPLIT, lib.VARIANT_DW_WALK)
+    cases = list(itertools.product((0, 1), ((17, 17), (2, 17), (2, 2), (1, 1)), (96, 4096, 32768, 262144, 262400, 526336, 2621440), variants, (0, 1), (256, 40)))
+    assert len(want) == len(cases) == 1120
+    forms = set()
+    for net, (pf, pb), P, var, live, cus in cases:
+        key = f"{net},{pf},{pb},{P},{var},{live},{cus}"
+        o = (ctypes.c_longlong * 80)()
+        rc = l.lush_debug_dw_plan(net, pf, pb, P, var, live, cus, o)
+        if want[key] is None:
+            assert rc != 0 and live and (net == 1 or var), key
+            continue
+        assert rc == 0, (key, l.lush_last_error())
+        n, per_job, Ppad, pps, gx, gy, cursors = o[:7]
+        got = list(o)[:7 + 6 * n] + [o[79]]
+        assert got == want[key], (key, got, want[key])
+        assert all(w == -1 for w in list(o)[7 + 6 * n:79]), key
+        jobs = [list(o)[7 + 6 * i:13 + 6 * i] for i in range(n)]      # n_out, k_in, k2_in, pe_mode, pps, first
+        first = [j[5] for j in jobs] + [o[79]]
+        assert Ppad == (P + 255) // 256 * 256 and pps % 32 == 0 and all(j[4] % 32 == 0 for j in jobs), key
+        assert gy == (n if per_job == 1 else 1) and cursors == (per_job == 3), key
+        if per_job in (2, 3):
+            assert first[0] == 0 and first[n] == gx and all(b > a for a, b in zip(first, first[1:])), (key, first)      # every job has a workgroup
+        assert (per_job == 1) == (Ppad <= MAX_PTS and not live), key
+        if per_job == 3:
+            assert Ppad > MAX_PTS and not var & lib.VARIANT_DW_WALK and Ppad % 256 == 0, key
+        forms.add(per_job)
+    assert forms == {0, 1, 2, 3}      # the cases reach every form
+    o = (ctypes.c_longlong * 80)()
+    assert l.lush_debug_dw_plan(0, 3, 3, 4096, 0, 0, 256, o) != 0 and b"three planes" in l.lush_last_error()      # one launch per layer: no plan
+    assert l.lush_debug_dw_plan(0, 17, 17, 1 << 27, 0, 0, 256, o) != 0 and l.lush_debug_dw_plan(0, 17, 17, 4096, 0, 0, 0, o) != 0

@@ -1170,6 +1170,59 @@ def test_pack_plan_equals_per_network_packing(diag, planes):
     assert diag.util.relerr(g1, tr2.flat.grad) < 2e-4
 
 
+PACK_CASES = [(net, planes, variant) for net in (0, 1) for planes in (1, 2, 3, 17) for variant in (-1, 0, 1, 4)]      # (1, 4: FWD_HALF, BWD_512)
+
+
+def _pack_tensors(net):
+    """The parameter tensors of synth.all_weights' coarse NeRF (net 0) / noise net (net 1) on the device, in lib.mlp_struct's order."""
+    from lush_nerf_amd import synth
+    w, prefix, nl = synth.all_weights(30, 11), ("mlp_coarse", "mlp_noise_coarse")[net], (8, 4)[net]
+    names = [f"pts_linears.{l}" for l in range(nl)] + ["views_linears.0", "feature_linear", "alpha_linear", "rgb_linear"]
+    return [torch.from_numpy(w[f"{prefix}.{n}.{k}"]).to("cuda:0").contiguous() for n in names for k in ("weight", "bias")]
+
+
+def _sha256(t):
+    import hashlib
+    return hashlib.sha256(t.cpu().numpy().tobytes()).hexdigest()
+
+
+def _pack_digest(lib, net, planes, variant, tensors):
+    """SHA-256 of a zero-filled packed buffer after lush_mlp_pack_for, or None where the library refuses the combination."""
+    import ctypes as C
+    from lush_nerf_amd import ops
+    buf = torch.zeros(lib.load().lush_mlp_packed_bytes(net, planes), dtype=torch.uint8, device="cuda:0")
+    st = lib.mlp_struct(tensors, (8, 4)[net])
+    rc = lib.load().lush_mlp_pack_for(net, planes, C.byref(st), lib.ptr(buf), variant, ops._stream())
+    torch.cuda.synchronize()
+    return None if rc else _sha256(buf)
+
+
+def test_packed_weights_are_byte_identical_to_the_recorded_ones(diag):
+    """The pack tables (lush_abi.hip: one stream builder for the uncut, the 128-row-half and the 64-row-quarter copies) put every
+    byte where the four hand-written builders they replace put it: SHA-256 of the whole zero-filled buffer after lush_mlp_pack_for,
+    against tests/pack_digests.json (recorded on an MI355X from the build before the builders were merged, which refused none
+    of the combinations), for both nets, every plane code and every copy selection; and the one-launch pack plan of the coarse + noise
+    pair writes the same bytes."""
+    import json
+    import os
+    from lush_nerf_amd import ops
+    want = json.load(open(os.path.join(os.path.dirname(os.path.abspath(__file__)), "pack_digests.json")))
+    assert sorted(want) == sorted(f"{n},{p},{v}" for n, p, v in PACK_CASES)
+    tensors = [_pack_tensors(0), _pack_tensors(1)]
+    for net, planes, variant in PACK_CASES:
+        assert _pack_digest(diag.lib, net, planes, variant, tensors[net]) == want[f"{net},{planes},{variant}"], (net, planes, variant)
+    for planes, variant in sorted({(p, v) for _, p, v in PACK_CASES}):
+        if want[f"0,{planes},{variant}"] is None or want[f"1,{planes},{variant}"] is None:
+            continue
+        plan = ops.PackPlan([(net, planes, tensors[net], variant) for net in (0, 1)])
+        for t in plan.buffers.values():
+            t.zero_()
+        plan.run()
+        torch.cuda.synchronize()
+        for net in (0, 1):
+            assert _sha256(plan.buffers[(tensors[net][0].data_ptr(), planes)]) == want[f"{net},{planes},{variant}"], ("plan", net, planes, variant)
+
+
 def test_wide_backward_rows_match_the_half_row_kernel(diag):
     """mlp_wide_bwd_kernel against mlp_chain_bwd_half_kernel (LUSH_VARIANT_BWD_HALF), element by element on what the chain
     leaves behind: every dZ_l row the weight-gradient GEMMs read, the dZv rows with the head gradients in their extra columns,
