@@ -83,6 +83,15 @@ int lush_composite_bwd(const float* raw, const float* z, const float* rays, int 
                        const float* g_rgb, const float* g_depth, const float* g_acc,
                        float* draw, float* drays, float* block_max, float* zero_buf, long long zero_n, int init_drays,
                        lush_stream_t stream);
+/* The COMPLETE backward of lush_composite_fwd (NeRFAll.raw2outputs as a public method: compositing on the caller's own z):
+ * upstream gradients of all five results -- g_rgb [R][3], g_density [R][S-1], g_acc [R], g_weights [R][S], g_depth [R], any of
+ * them NULL (= 0) -- and the forward's raw, z, rays (rays_d in columns 3..5), noise, noise_std, near_mask, white_bkgd.
+ * d_raw [R][S][4], d_z [R][S] and d_rays_d [R][3] are written, every element.  The near mask is a step in z and gives no d_z;
+ * the last sample has alpha = 1, so its d_raw[.., 3] is 0.  2 <= S <= 256 like the forward; formulas: DESIGN.md section 4. */
+int lush_composite_bwd_full(const float* raw, const float* z, const float* rays, int R, int S,
+                            const float* noise, float noise_std, float near_mask, int white_bkgd,
+                            const float* g_rgb, const float* g_density, const float* g_acc, const float* g_weights,
+                            const float* g_depth, float* d_raw, float* d_z, float* d_rays_d, lush_stream_t stream);
 /* scale2 = {s, 1/s}: s = the power of two that puts max(block_max[0..n)) into [8, 16); 1 when the maximum is 0 or not finite
  * (the rule of the loss-scaled fp16 gradient chain). */
 int lush_loss_scale(const float* block_max, int n, float* scale2, lush_stream_t stream);
@@ -344,6 +353,13 @@ int lush_mlp_bwd_weights(int net, int planes_f, int planes_b, int R, int S, cons
  * -> drays [R][11] accumulate (o: 0..2, d: 3..5, viewdir: 8..10). */
 int lush_ray_grad_reduce(const float* dpts, const float* z, int R, int S, float* drays,
                          lush_stream_t stream);
+/* Free points (NeRFAll.mlpforward / mlpforward_noise as public methods, models/lushnerf.py:234-293): pts [R][S][3] and
+ * dirs [R][3] -> pseudo-rays [R*S][11] with rows [pt, 0,0,0, 0, 1, dir] and z [R*S] = 0, the (R*S, 1) launch of lush_mlp_fwd /
+ * lush_mlp_bwd: the kernels form a point as o + d*z with a separate multiply and add, so pt + 0*0 is the caller's point bit
+ * for bit.  lush_points_grad turns that launch's dpts [R*S][8] into d_pts [R][S][3] and d_dirs [R][3] = the sum over S, in a
+ * fixed order without atomics (two runs give the same bits); both outputs are written, every element.  R * S < 2^27. */
+int lush_points_pack(const float* pts, const float* dirs, int R, int S, float* rays, float* z, lush_stream_t stream);
+int lush_points_grad(const float* dpts, int R, int S, float* d_pts, float* d_dirs, lush_stream_t stream);
 
 /* Live points (round 5).  A sample whose density pre-activation the ReLU of raw2outputs clamps (models/lushnerf.py:313:
  * relu(raw[..., 3] + noise)) has alpha = 0, weight = 0 and d alpha / d raw = 0: its d_raw row is exactly zero and nothing flows

@@ -3,6 +3,7 @@
 // scans/reductions along the ray are wave-level shuffles.
 #include "lush_common.h"
 #include "lush_host.h"
+#include "lush_composite.h"
 #include <type_traits>
 #include "../../include/lush_march.h"
 
@@ -17,8 +18,6 @@ int set_hip_error(hipError_t e, const char* what, const char* file, int line) {
     g_err = std::string(hipGetErrorString(e)) + " in " + what + " at " + file + ":" + std::to_string(line);
     return -2;
 }
-
-constexpr int RAYS_PER_BLOCK = 4;   // 4 waves per workgroup, one ray each
 
 // torch.linspace(0, 1, n)[i] as ATen computes it in fp32
 // (aten/src/ATen/native/RangeFactories: step=(end-start)/(n-1); first half counts
@@ -59,67 +58,7 @@ __global__ void zfixed_kernel(const float* __restrict__ rays, int R, int S, int 
     if (ray < R) z[ray] = zgrid_at(rays[ray * 11 + 6], rays[ray * 11 + 7], index, S, lindisp);
 }
 
-// ---------------------------------------------------------------- compositing
-// Lane l owns samples l*SPL .. l*SPL+SPL-1.
-struct CompIn {
-    const float *raw, *z, *rays, *noise;
-    int R, S;
-    float noise_std, near_mask;
-    int white_bkgd;
-};
-
-template <int SPL>
-__device__ __forceinline__ void comp_load(const CompIn& c, int ray, int lane, float (&alpha)[SPL], float (&dist)[SPL],
-                                          float (&dens)[SPL], float (&gate)[SPL], float (&zz)[SPL],
-                                          float (&rgbv)[SPL][3], float& norm, bool* bad_raw = nullptr) {
-    const float* rr = c.rays + (long long)ray * 11;
-    norm = sqrtf(rr[3] * rr[3] + rr[4] * rr[4] + rr[5] * rr[5]);
-#pragma unroll
-    for (int e = 0; e < SPL; ++e) {
-        const int j = lane * SPL + e;
-        alpha[e] = 0.f; dist[e] = 0.f; dens[e] = 0.f; gate[e] = 0.f; zz[e] = 0.f;
-        rgbv[e][0] = rgbv[e][1] = rgbv[e][2] = 0.f;
-        if (j < c.S) {
-            const long long p = (long long)ray * c.S + j;
-            const float4 rw = *reinterpret_cast<const float4*>(c.raw + p * 4);
-            if (bad_raw)     // NaN or Inf in the network output (models/lushnerf.py:474-478 checks ret['raw'])
-                *bad_raw |= !(fabsf(rw.x) <= 3.402823466e38f) || !(fabsf(rw.y) <= 3.402823466e38f) ||
-                            !(fabsf(rw.z) <= 3.402823466e38f) || !(fabsf(rw.w) <= 3.402823466e38f);
-            zz[e] = c.z[p];
-            rgbv[e][0] = 1.f / (1.f + expf(-rw.x));
-            rgbv[e][1] = 1.f / (1.f + expf(-rw.y));
-            rgbv[e][2] = 1.f / (1.f + expf(-rw.z));
-            if (j < c.S - 1) {
-                const float znext = c.z[p + 1];
-                dist[e] = (znext - zz[e]) * norm;
-                float pre = rw.w;
-                if (c.noise != nullptr && c.noise_std > 0.f)
-                    pre += c.noise[(long long)ray * (c.S - 1) + j] * c.noise_std;
-                float g = pre > 0.f ? 1.f : 0.f;
-                float d = fmaxf(pre, 0.f);
-                if (c.near_mask >= 0.f && !(znext > c.near_mask)) { d = 0.f; g = 0.f; }
-                dens[e] = d; gate[e] = g;
-                alpha[e] = 1.f - expf(-d * dist[e]);
-            } else {
-                alpha[e] = 1.f;   // last sample: models/lushnerf.py:338
-            }
-        }
-    }
-}
-
-// transmittance T_j = prod_{k<j} (1 - alpha_k)
-template <int SPL>
-__device__ __forceinline__ void comp_trans(const float (&alpha)[SPL], int lane, float (&T)[SPL]) {
-    float loc = 1.f;
-#pragma unroll
-    for (int e = 0; e < SPL; ++e) { T[e] = loc; loc *= (1.f - alpha[e]); }
-    float incl = wave_incl_prod(loc, lane);
-    float excl = __shfl_up(incl, 1, 64);
-    if (lane == 0) excl = 1.f;
-#pragma unroll
-    for (int e = 0; e < SPL; ++e) T[e] *= excl;
-}
-
+// ---------------------------------------------------------------- compositing (loads and transmittance: lush_composite.h)
 template <int SPL>
 __global__ __launch_bounds__(RAYS_PER_BLOCK * 64) void composite_fwd_kernel(CompIn c, float* __restrict__ rgb,
         float* __restrict__ depth, float* __restrict__ acc, float* __restrict__ weights, float* __restrict__ density,

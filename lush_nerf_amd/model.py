@@ -214,6 +214,52 @@ class NeRFAll(nn.Module):
                                   torch.is_grad_enabled(), self.hooks,
                                   *self.mlp_noise_coarse.tensors())
 
+    # ------------------------------------------------------------------ the field and the compositing on their own
+    def _field(self, inputs, viewdirs, mlp):
+        """raw [R,S,4] of one of this model's networks at free points [R,S,3] with one direction per ray [R,3] (ops.FieldQuery)."""
+        if viewdirs is None:
+            raise NotImplementedError("viewdirs=None is not built (every config sets use_viewdirs)")
+        nets = [(self.mlp_coarse, ops.NET_NERF), (self.mlp_fine, ops.NET_NERF), (self.mlp_noise_coarse, ops.NET_NOISE)]
+        net = next((code for m, code in nets if m is not None and mlp is m), None)
+        if net is None:
+            raise ValueError("mlp must be this model's mlp_coarse, mlp_fine or mlp_noise_coarse")
+        if inputs.dim() != 3 or inputs.shape[-1] != 3:
+            raise ValueError(f"inputs must be [R, S, 3] points, got {tuple(inputs.shape)}")
+        if viewdirs.dim() != 2 or viewdirs.shape[-1] != 3 or viewdirs.shape[0] != inputs.shape[0]:
+            raise ValueError(f"viewdirs must be [R, 3], one direction per ray of inputs {tuple(inputs.shape)}, got {tuple(viewdirs.shape)}")
+        precision = self.precision.noise() if net == ops.NET_NOISE else self.precision
+        return ops.FieldQuery.apply(inputs, viewdirs, net, precision, torch.is_grad_enabled(), self.hooks, *mlp.tensors())
+
+    def mlpforward(self, inputs, viewdirs, mlp, force_naive, inference, netchunk=1024 * 64):
+        """models/lushnerf.py:234-266: inputs [R,S,3], viewdirs [R,3] (used as given, not normalised) -> raw [R,S,4] of the
+        8x256 nets, [R,S,3] of the noise net.  `force_naive` and `inference` only select the use_awp return form in the
+        reference and `netchunk` does not change results: accepted and unused (one launch takes up to 2^27 - 1 points)."""
+        raw = self._field(inputs, viewdirs, mlp)
+        return raw[..., :3] if mlp is self.mlp_noise_coarse else raw
+
+    def mlpforward_noise(self, inputs, viewdirs, mlp, force_naive, inference, netchunk=1024 * 64):
+        """models/lushnerf.py:268-293: the network at sample 16 of every ray, inputs [N,S,3] -> [N,3]."""
+        if viewdirs is None:
+            raise NotImplementedError("viewdirs=None is not built (every config sets use_viewdirs)")
+        if inputs.dim() != 3 or inputs.shape[-1] != 3:
+            raise ValueError(f"inputs must be [N, S, 3] points, got {tuple(inputs.shape)}")
+        return self.mlpforward(inputs[:, 16][:, None], viewdirs, mlp, force_naive, inference, netchunk)[:, 0]
+
+    def raw2outputs(self, raw, z_vals, rays_d, raw_noise_std=0, white_bkgd=False, pytest=False, noise=None):
+        """models/lushnerf.py:296-352 -> (rgb_map, density, acc_map, weights, depth_map), differentiable in raw, z_vals and
+        rays_d.  `noise` [R,S-1]: the N(0,1) draw (:322) given explicitly; otherwise raw_noise_std > 0 takes one Philox draw
+        of the model's counter.  `pytest` is accepted and unused, as on the render methods."""
+        near_mask = -1.0
+        if (not self.training) and getattr(self.args, "render_rmnearplane", 0) > 0:
+            near_mask = self.args.render_rmnearplane / 128
+        std = float(raw_noise_std)
+        if std > 0 and noise is None:
+            if not z_vals.is_cuda:
+                raise RuntimeError("lush_nerf_amd ops need CUDA/HIP tensors (no CPU path)")
+            R, S = z_vals.shape
+            noise = ops.march_draws(R, S, 0, 0., std, z_vals.device, stream_id=self.rng_stream, hooks=self.hooks)['noise_c']
+        return ops.Composite.apply(raw, z_vals, rays_d, noise, std, near_mask, bool(white_bkgd))
+
     # ------------------------------------------------------------------ render_rays trio
     def render_rays(self, ray_batch, N_samples, img_idx=None, retraw=False, lindisp=False, perturb=0.,
                     N_importance=0, white_bkgd=False, raw_noise_std=0., pytest=False, force_naive=False,

@@ -706,6 +706,106 @@ class NoiseMlp(torch.autograd.Function):
         return (None, None, None, None, None, None, None, *grads)
 
 
+# ----------------------------------------------------------------------------- the field at free points, compositing on free z
+def points_pack(pts, dirs):
+    """pts [R,S,3], dirs [R,3] -> pseudo-rays [R*S,11] = [pt, 0,0,0, 0, 1, dir] and z [R*S,1] = 0 (lush_points_pack): the (P,1)
+    launch of the MLP kernels whose point o + d*z is the caller's, bit for bit."""
+    R, S = pts.shape[0], pts.shape[1]
+    rays = torch.empty(R * S, 11, dtype=torch.float32, device=pts.device)
+    z = torch.empty(R * S, 1, dtype=torch.float32, device=pts.device)
+    lib.call("lush_points_pack", lib.ptr(pts), lib.ptr(dirs), R, S, lib.ptr(rays), lib.ptr(z), _stream())
+    return rays, z
+
+
+def points_grad(dpts, R, S):
+    """dpts [R*S,8] of the gradient chain -> d(points) [R,S,3], d(directions) [R,3] = the sum over S in a fixed order (lush_points_grad)."""
+    d_pts = torch.empty(R, S, 3, dtype=torch.float32, device=dpts.device)
+    d_dirs = torch.empty(R, 3, dtype=torch.float32, device=dpts.device)
+    lib.call("lush_points_grad", lib.ptr(dpts), R, S, lib.ptr(d_pts), lib.ptr(d_dirs), _stream())
+    return d_pts, d_dirs
+
+
+class FieldQuery(torch.autograd.Function):
+    """NeRFAll.mlpforward / mlpforward_noise on points the caller chose (models/lushnerf.py:234-293): pts [R,S,3], dirs [R,3]
+    -> raw [R,S,4] of `net` (column 3 is 0 for the noise net).  Points, directions and parameters receive gradients."""
+
+    @staticmethod
+    def forward(ctx, pts, dirs, net, precision: Precision, want_grad, hooks: Optional[Hooks], *params):
+        pts, dirs = _f32(pts), _f32(dirs)
+        tensors = [_f32(p) for p in params]
+        R, S = pts.shape[0], pts.shape[1]
+        rays, z = points_pack(pts, dirs)
+        pk = _packed_for(hooks, tensors, precision.fwd)
+        if pk is None:
+            pk = mlp_pack(net, precision.fwd, tensors)
+        need = bool(want_grad) and any(ctx.needs_input_grad)
+        raw, stash = mlp_forward(net, precision.fwd, tensors, pk, rays, z, need, stash_code(precision.fwd, precision.bwd),
+                                 precision.variant, hooks.timer if hooks is not None else None)
+        if hooks is not None and hooks.keep is not None:
+            hooks.keep.update(stash_field=stash, P_field=R * S)
+        if need:
+            ctx.save_for_backward(rays, z, stash, *tensors)
+        ctx.net, ctx.precision, ctx.hooks, ctx.shape = net, precision, hooks, (R, S)
+        return raw.view(R, S, 4)
+
+    @staticmethod
+    def backward(ctx, g):
+        pr, net = ctx.precision, ctx.net
+        R, S = ctx.shape
+        t = ctx.saved_tensors
+        rays, z, stash = t[0], t[1], t[2]
+        tensors = list(t[3:])
+        draw = _f32(g).reshape(R * S, 4)
+        pk = _packed_for(ctx.hooks, tensors, pr.bwd)
+        if pk is None:
+            pk = mlp_pack(net, pr.bwd, tensors)
+        grads, dpts = mlp_backward(net, stash_code(pr.fwd, pr.bwd), pr.bwd, tensors, pk, rays, z, draw, stash,
+                                   sink=grad_sink(tensors, ctx.hooks), variant=pr.variant)
+        d_pts, d_dirs = points_grad(dpts, R, S)
+        if net == NET_NOISE:
+            o = 2 * _NL[NET_NOISE] + 4   # alpha_linear is dead in NeRF_Noise (helpers:496,505,512): grad None
+            grads[o] = None
+            grads[o + 1] = None
+        return (d_pts, d_dirs, None, None, None, None, *grads)
+
+
+class Composite(torch.autograd.Function):
+    """NeRFAll.raw2outputs on the caller's own z (models/lushnerf.py:296-352): raw [R,S,4], z_vals [R,S], rays_d [R,3],
+    noise [R,S-1] N(0,1) or None -> (rgb_map, density, acc_map, weights, depth_map), differentiable in raw, z_vals and rays_d
+    through all five (lush_composite_fwd / lush_composite_bwd_full)."""
+
+    @staticmethod
+    def forward(ctx, raw, z_vals, rays_d, noise, noise_std, near_mask, white_bkgd):
+        raw, z, rays_d = _f32(raw), _f32(z_vals), _f32(rays_d)
+        noise = _f32(noise) if (noise is not None and noise_std > 0) else None
+        R, S = z.shape
+        if tuple(raw.shape) != (R, S, 4) or tuple(rays_d.shape) != (R, 3) or (noise is not None and tuple(noise.shape) != (R, S - 1)):
+            raise ValueError(f"raw2outputs: raw [R,S,4], z_vals [R,S], rays_d [R,3], noise [R,S-1] expected, got "
+                             f"{tuple(raw.shape)}, {tuple(z.shape)}, {tuple(rays_d.shape)}" + (f", {tuple(noise.shape)}" if noise is not None else ""))
+        batch = torch.zeros(R, 11, dtype=torch.float32, device=z.device)      # the kernels read rays_d from columns 3..5 of a ray batch
+        batch[:, 3:6] = rays_d
+        cfg = MarchCfg(N_samples=S, raw_noise_std=float(noise_std), white_bkgd=bool(white_bkgd), near_mask=float(near_mask))      # (no fault word)
+        rgb, depth, acc, weights, density = composite_fwd(raw, z, batch, noise, cfg)
+        ctx.save_for_backward(raw, z, batch, *([noise] if noise is not None else []))
+        ctx.cfg = cfg
+        return rgb, density, acc, weights, depth
+
+    @staticmethod
+    def backward(ctx, g_rgb, g_density, g_acc, g_weights, g_depth):
+        t = ctx.saved_tensors
+        raw, z, batch = t[0], t[1], t[2]
+        noise = t[3] if len(t) > 3 else None
+        cfg = ctx.cfg
+        R, S = z.shape
+        d_raw = torch.empty(R, S, 4, dtype=torch.float32, device=z.device)
+        d_z = torch.empty(R, S, dtype=torch.float32, device=z.device)
+        d_rays_d = torch.empty(R, 3, dtype=torch.float32, device=z.device)
+        g = [_opt(x) for x in (g_rgb, g_density, g_acc, g_weights, g_depth)]
+        lib.call("lush_composite_bwd_full", lib.ptr(raw), lib.ptr(z), lib.ptr(batch), R, S, lib.ptr(noise), float(cfg.raw_noise_std),
+                 float(cfg.near_mask), int(cfg.white_bkgd), *(lib.ptr(x) for x in g), lib.ptr(d_raw), lib.ptr(d_z), lib.ptr(d_rays_d), _stream())
+        return d_raw, d_z, d_rays_d, None, None, None, None
+
+
 # ----------------------------------------------------------------------------- blur kernel
 RBK_ACT = 512
 RBK_RVW = 32
