@@ -959,78 +959,97 @@ struct GrpStream {
     const char* src2;       // X2 (waves 0..3 when the job has one)
     unsigned stride2, voff2, dst2;
     bool on2;
-    // X2 re-encoded instead of read (DwGroup::xd, DwJob::pe_mode): this lane's 16-byte chunk of gamma(.) of its tile row
+    // X2 re-encoded instead of read (DwGroup::xd, DwJob::pe_mode): this lane's argument unit of gamma(.) of its tile rows (dw_pe_col below)
     const char* xd;         // uniform; null: X2 is read.  Else: the slice's first point's quadruple (x or viewdir) in DwGroup::xd
     long long pe_last;      // last valid point of the array relative to the slice's first (reads are clamped to it)
-    unsigned pe_row16;      // per-lane (waves 0..3): 16 x the lane's tile row = its byte offset inside a tile's 512 bytes of quadruples
-    unsigned pe_dst;        // per-lane LDS byte offset of the chunk inside a stage
-    int pe_gch, pe_nvalid;  // source chunk (8 columns) of gamma(.), its number of valid columns (63 / 27)
+    unsigned pe_src;        // per-lane byte offset, inside a tile's 512 bytes of quadruples, of the coordinate its unit uses (first trip's row)
+    unsigned pe_dst[2];     // per-lane LDS byte offsets inside a stage of its two columns (first trip's row)
+    float pe_scale;         // per-lane: 2^k of its argument; 0: the unit passes coordinates through or is padding
+    unsigned pe_keep;       // per-lane: 0xffff in the half of each of its two columns that is < the block's valid columns (63 / 27)
 };
 // Quadruples (16 bytes per point) of GRP_PE_CHUNK points at a time through two LDS buffers behind the stages: one LDS-DMA per wave
 // and chunk, issued a whole chunk (16 tiles) ahead, so the ordinary ring waits cover it and no wait of its own stands in the loop.
 constexpr int GRP_PE_CHUNK = 512, GRP_PE_BYTES = GRP_PE_CHUNK * 16;
 
-// 8 columns [8 gch, 8 gch + 8) of gamma(c) = [c, sin(2^k c), cos(2^k c) ...] (utils/run_lushnerf_helpers.py:334-361) as fp16 to
-// `dst` (LDS), bit for bit what wd_pe_tile (lush_mlp_wide.hip) wrote into the forward's LDS image: the same range reduction, the
-// same hardware sin / cos, the same rounding.  Columns >= nvalid are zero.  One pair of columns per trip of a ROLLED loop: unrolled,
-// the compiler evaluated the 40 lane predicates of the 8 columns up front (106 scalar registers spilled).
-__device__ __forceinline__ void dw_pe_write(char* dst, const f32x4 c, int gch, int nvalid) {
-    float hi[3], lo[3];
-#pragma unroll
-    for (int i = 0; i < 3; ++i) rev_split(c[i], &hi[i], &lo[i]);
-#pragma unroll 1
-    for (int p = 0; p < 4; ++p) {
-        float v[2];
-#pragma unroll
-        for (int t = 0; t < 2; ++t) {
-            const int j = 8 * gch + 2 * p + t;
-            const int q = j < 3 ? 0 : j - 3;
-            const int k = (q * 43) >> 8;                 // q / 6 for 0 <= q < 64
-            const int r = q - 6 * k;
-            const int i = j < 3 ? j : (r < 3 ? r : r - 3);
-            const float ci = i == 0 ? c[0] : (i == 1 ? c[1] : c[2]);
-            const float h_ = i == 0 ? hi[0] : (i == 1 ? hi[1] : hi[2]);
-            const float l_ = i == 0 ? lo[0] : (i == 1 ? lo[1] : lo[2]);
-            const float s = __builtin_ldexpf(1.0f, k);
-            const float rr = __builtin_amdgcn_fractf(h_ * s) + l_ * s;
-            const float sc = r < 3 ? __builtin_amdgcn_sinf(rr) : __builtin_amdgcn_cosf(rr);
-            v[t] = j < 3 ? ci : (j < nvalid ? sc : 0.f);
-        }
-        unsigned w_[1];
-        split_pair<1, DT_F16>(v[0], v[1], w_);
-        *reinterpret_cast<unsigned*>(dst + 4 * p) = w_[0];
-    }
+// gamma(c) = [c, sin(2^k c), cos(2^k c) ...] (utils/run_lushnerf_helpers.py:334-361) of a tile's 32 points as fp16 into the stage's X2
+// tile, bit for bit what wd_pe_tile (lush_mlp_wide.hip) wrote into the forward's LDS image: the same rev_split, the same
+// fract(hi 2^k) + lo 2^k, the same hardware sin / cos on it, the same rounding; zeros in columns >= nvalid.
+// Who encodes what never changes inside a job, so it is worked out ONCE per job (GrpStream::pe_*), not per value and tile:
+//  * a lane is one ARGUMENT UNIT u = lane & 31 of a row: u < 30 is (frequency u / 3, coordinate u % 3) and yields that argument's
+//    sine AND cosine (columns 3 + 6 k + i and + 3: one range reduction for two values, one transcendental per value); unit 30 passes
+//    coordinates 0 and 1 through (columns 0, 1), unit 31 coordinate 2 and the zero of column 63.  A lane reads and splits only the
+//    coordinate it uses; its power of two is a register (0 marks a unit that is not an argument, or whose columns are padding).
+//  * wave w takes rows 8 (w >> 1) + 2 (w & 1) + {0, 1, 4, 5}: lanes 0..31 the row, lanes 32..63 the row + 1, and a second trip four
+//    rows below.  All four rows swizzle alike, so the second trip's addresses are the first's plus constants.
+//  * the LDS writes are 2 bytes wide; the 32 lanes of a half-wave write 32 different columns of ONE 128-byte row, i.e. every one of
+//    the 32 store banks once or twice within one dword: no conflict, as little as the 4-byte writes of 16 lanes per row (two rows
+//    of a half-wave on the same banks) this replaces; four store instructions per wave and tile instead of two.
+// Before: ~28 VALU instructions and both transcendentals per value (column -> frequency, coordinate, function by integer arithmetic
+// and select chains in every lane for every tile, all three coordinates split): ~120 per lane and tile.  Now ~16 per lane and trip.
+struct DwPeCol { int col, coord, freq, fn; };       // fn: 0 sine, 1 cosine, 2 the coordinate itself, 3 zero padding
+constexpr int DW_PE_UNITS = 32, DW_PE_TRIPS = 2, DW_PE_TRIP_ROWS = 4;
+constexpr int dw_pe_row(int w, int half, int trip) { return 8 * (w >> 1) + 2 * (w & 1) + half + DW_PE_TRIP_ROWS * trip; }
+constexpr DwPeCol dw_pe_col(int u, int f) {
+    if (u < 30) return DwPeCol{3 + 6 * (u / 3) + 3 * f + u % 3, u % 3, u / 3, f};
+    if (u == 30) return DwPeCol{f, f, 0, 2};
+    return f == 0 ? DwPeCol{2, 2, 0, 2} : DwPeCol{63, 0, 0, 3};
 }
-
-// The same for 4 columns [8 gch + 4 half, .. + 4): 8 bytes per lane, so that ALL eight waves share a tile's 32 rows x 64 columns
-// (16 lanes per row).  With four waves re-encoding 16 bytes per lane the other four idled behind them at the stage's barrier and
-// a workgroup spent 27 ns per point in its three re-encoding jobs (profiles/r05_dw_jobs.md) -- the jobs ran 1.3 x .. 1.9 x their
-// streaming time.
-__device__ __forceinline__ void dw_pe_write4(char* dst, const f32x4 c, int gch, int half, int nvalid) {
-    float hi[3], lo[3];
-#pragma unroll
-    for (int i = 0; i < 3; ++i) rev_split(c[i], &hi[i], &lo[i]);
-#pragma unroll 1
-    for (int p = 0; p < 2; ++p) {
-        float v[2];
-#pragma unroll
-        for (int t = 0; t < 2; ++t) {
-            const int j = 8 * gch + 4 * half + 2 * p + t;
-            const int q = j < 3 ? 0 : j - 3;
-            const int k = (q * 43) >> 8;                 // q / 6 for 0 <= q < 64
-            const int r = q - 6 * k;
-            const int i = j < 3 ? j : (r < 3 ? r : r - 3);
-            const float ci = i == 0 ? c[0] : (i == 1 ? c[1] : c[2]);
-            const float h_ = i == 0 ? hi[0] : (i == 1 ? hi[1] : hi[2]);
-            const float l_ = i == 0 ? lo[0] : (i == 1 ? lo[1] : lo[2]);
-            const float s = __builtin_ldexpf(1.0f, k);
-            const float rr = __builtin_amdgcn_fractf(h_ * s) + l_ * s;
-            const float sc = r < 3 ? __builtin_amdgcn_sinf(rr) : __builtin_amdgcn_cosf(rr);
-            v[t] = j < 3 ? ci : (j < nvalid ? sc : 0.f);
+constexpr unsigned dw_pe_off(int row, int col) {     // byte offset of (row, col) in the X2 tile: tr_off_x2's swizzle
+    return (unsigned)(row * GRP_X2_ROWB + ((2 * col) ^ (((row >> 1) & 1) << 6)));
+}
+constexpr bool dw_pe_map_covers_the_tile() {
+    int n[DMA_KT][64] = {};
+    for (int w = 0; w < DW_THREADS2 / 64; ++w)
+        for (int half = 0; half < 2; ++half)
+            for (int trip = 0; trip < DW_PE_TRIPS; ++trip)
+                for (int u = 0; u < DW_PE_UNITS; ++u)
+                    for (int f = 0; f < 2; ++f) {
+                        const int row = dw_pe_row(w, half, trip), col = dw_pe_col(u, f).col;
+                        if (row < 0 || row >= DMA_KT || col < 0 || col >= 64) return false;
+                        ++n[row][col];
+                        // the second trip's address is the first's plus a constant (the rows swizzle alike)
+                        if (dw_pe_off(row, col) != dw_pe_off(dw_pe_row(w, half, 0), col) + (unsigned)(trip * DW_PE_TRIP_ROWS * GRP_X2_ROWB)) return false;
+                    }
+    for (int r = 0; r < DMA_KT; ++r)
+        for (int c = 0; c < 64; ++c)
+            if (n[r][c] != 1) return false;                      // every (row, column) exactly once
+    for (int u = 0; u < DW_PE_UNITS; ++u)
+        for (int f = 0; f < 2; ++f) {                            // gamma = [c, sin(2^0 c), cos(2^0 c), sin(2^1 c), ...], 3 columns each
+            const DwPeCol c = dw_pe_col(u, f);
+            const int q = c.col - 3;
+            if (c.col < 3) { if (c.fn != 2 || c.coord != c.col) return false; }
+            else if (c.col == 63) { if (c.fn != 3) return false; }
+            else if (c.fn != (q % 6) / 3 || c.freq != q / 6 || c.coord != q % 3) return false;
+            // a lane reads quadruple entries coord and coord + 1 of its FIRST column: a pass-through unit's second value is the latter
+            if (dw_pe_col(u, 0).coord > 2 || (f == 1 && c.fn == 2 && c.coord != dw_pe_col(u, 0).coord + 1)) return false;
+            if (f == 1 && c.fn < 2 && (c.coord != dw_pe_col(u, 0).coord || c.freq != dw_pe_col(u, 0).freq)) return false;   // one argument
         }
+    return true;
+}
+static_assert(DMA_KT == 32 && DW_THREADS2 == 512 && GRP_X2_ROWB == 128, "the re-encoding's map is written for 32 x 64 tiles and eight waves");
+static_assert(dw_pe_map_covers_the_tile(), "every (row, column) of the X2 tile once, each column with gamma's coordinate, frequency and function");
+
+// One tile: `xq` = the tile's quadruples in LDS (16 bytes per point), `x2t` = the stage's X2 tile.  (An entry a lane reads but does
+// not use -- the quadruple's fourth word may hold the queue's claim -- never reaches arithmetic: it is selected away or masked as bits.)
+__device__ __forceinline__ void dw_pe_encode(char* x2t, const char* xq, unsigned src, const unsigned (&dst)[2], float scale, unsigned keep) {
+    const bool arg = scale != 0.f;
+    float x0[DW_PE_TRIPS], x1[DW_PE_TRIPS];
+#pragma unroll
+    for (int trip = 0; trip < DW_PE_TRIPS; ++trip) {      // (both trips' reads first: one LDS round trip in front of the arithmetic)
+        const float* c = reinterpret_cast<const float*>(xq + src + trip * DW_PE_TRIP_ROWS * 16);
+        x0[trip] = c[0];
+        x1[trip] = c[1];
+    }
+#pragma unroll
+    for (int trip = 0; trip < DW_PE_TRIPS; ++trip) {
+        float hi, lo;
+        rev_split(x0[trip], &hi, &lo);
+        const float r = __builtin_amdgcn_fractf(hi * scale) + lo * scale;
         unsigned w_[1];
-        split_pair<1, DT_F16>(v[0], v[1], w_);
-        *reinterpret_cast<unsigned*>(dst + 4 * p) = w_[0];
+        split_pair<1, DT_F16>(arg ? __builtin_amdgcn_sinf(r) : x0[trip], arg ? __builtin_amdgcn_cosf(r) : x1[trip], w_);
+        const unsigned v = w_[0] & keep;
+        *reinterpret_cast<unsigned short*>(x2t + dst[0] + trip * DW_PE_TRIP_ROWS * GRP_X2_ROWB) = (unsigned short)v;
+        *reinterpret_cast<unsigned short*>(x2t + dst[1] + trip * DW_PE_TRIP_ROWS * GRP_X2_ROWB) = (unsigned short)(v >> 16);
     }
 }
 
@@ -1134,8 +1153,8 @@ __device__ __forceinline__ void grp_stream(const GrpStream& st, const char* tile
         if constexpr (NV2 > 0) {
             if (PE && st.xd != nullptr) {
                 // re-encode this tile's X2 rows from the quadruples in LDS (chunk ti / 16, loaded a chunk ahead): every wave, 4 rows each
-                const f32x4 c = *reinterpret_cast<const f32x4*>(coords + ((ti >> 4) & 1) * GRP_PE_BYTES + (ti & 15) * (KT_ * 16) + st.pe_row16);
-                dw_pe_write4(const_cast<char*>(tiles) + slot * GRP_STAGE + st.pe_dst, c, st.pe_gch, lane & 1, st.pe_nvalid);
+                dw_pe_encode(const_cast<char*>(tiles) + slot * GRP_STAGE, coords + ((ti >> 4) & 1) * GRP_PE_BYTES + (ti & 15) * (KT_ * 16),
+                             st.pe_src, st.pe_dst, st.pe_scale, st.pe_keep);
             } else if (x2_wave) {
                 if (st.on2) dma16s_stream(src2, st.voff2, __builtin_amdgcn_readfirstlane(base + st.dst2));
                 src2 += st.stride2;
@@ -1399,17 +1418,20 @@ __device__ __forceinline__ void dw_group_body(const DwGroup& G) {
                 st.on[i] = gch * 8 < ncols;
             }
             st.src2 = nullptr; st.stride2 = 0; st.voff2 = 0; st.dst2 = 0; st.on2 = false;
-            st.xd = nullptr; st.pe_last = 0; st.pe_row16 = 0; st.pe_dst = 0; st.pe_gch = 0; st.pe_nvalid = 0;
+            st.xd = nullptr; st.pe_last = 0; st.pe_src = 0; st.pe_dst[0] = 0; st.pe_dst[1] = 0; st.pe_scale = 0.f; st.pe_keep = 0;
             if (has_x2 && G.xd != nullptr && A.pe_mode != 0) {      // (all waves: each moves its share of the quadruples)
                 st.xd = reinterpret_cast<const char*>(G.xd + p_begin * 8 + (A.pe_mode == 2 ? 4 : 0));
                 st.pe_last = (long long)Ppad - 1 - p_begin;
             }
-            if (st.xd != nullptr) {      // every wave: tile rows 4 w .. 4 w + 3, 16 lanes per row, 4 columns (8 bytes) per lane
-                const int row = 4 * w + (lane >> 4);
-                st.pe_gch = ((lane >> 1) & 7) ^ (((row >> 1) & 1) << 2);
-                st.pe_nvalid = A.k2_in;
-                st.pe_row16 = (unsigned)((row % KT) * 16);
-                st.pe_dst = (unsigned)(2 * DMA_OPER + 4 * w * GRP_X2_ROWB + lane * 8);
+            if (st.xd != nullptr) {      // every wave: four tile rows, 32 lanes per row, one argument unit (two columns) per lane
+                const int row = dw_pe_row(w, lane >> 5, 0);
+                const DwPeCol c0 = dw_pe_col(lane & 31, 0), c1 = dw_pe_col(lane & 31, 1);
+                const bool keep0 = c0.fn != 3 && c0.col < A.k2_in, keep1 = c1.fn != 3 && c1.col < A.k2_in;
+                st.pe_src = (unsigned)(row * 16 + c0.coord * 4);
+                st.pe_dst[0] = (unsigned)(2 * DMA_OPER) + dw_pe_off(row, c0.col);
+                st.pe_dst[1] = (unsigned)(2 * DMA_OPER) + dw_pe_off(row, c1.col);
+                st.pe_scale = c0.fn < 2 && (keep0 || keep1) ? __builtin_ldexpf(1.0f, c0.freq) : 0.f;
+                st.pe_keep = (keep0 ? 0xffffu : 0u) | (keep1 ? 0xffff0000u : 0u);
             } else if (x2_wave) {
                 const int row = 8 * w + (lane >> 3);
                 const int gch = (lane & 7) ^ (((row >> 1) & 1) << 2);

@@ -409,7 +409,7 @@ __device__ __noinline__ void wd_pe_tile(char* peimg, const float* rays, const fl
     const long long gpt = tile_pt0 + tid;
     float x[3] = {0.f, 0.f, 0.f}, d[3] = {0.f, 0.f, 0.f};
     if (gpt < P) point_of(rays, z, S, live ? (long long)live[gpt] : gpt, x, d);      // (a live-point launch: its i-th point is grid point live[i])
-    if (xd != nullptr) {      // what the weight gradients re-encode (dw_pe_write, lush_mlp.hip): 32 bytes instead of the 256-byte row
+    if (xd != nullptr) {      // what the weight gradients re-encode (dw_pe_encode, lush_mlp.hip): 32 bytes instead of the 256-byte row
         float4* o = reinterpret_cast<float4*>(xd + gpt * 8);
         o[0] = make_float4(x[0], x[1], x[2], 0.f);
         o[1] = make_float4(d[0], d[1], d[2], 0.f);
