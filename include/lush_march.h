@@ -4,7 +4,9 @@
  * The reference has no FFI; its boundary for this path is a set of Python
  * methods on an nn.Module.  Each entry point below names
  * the reference code it replaces (file:line into the LuSh-NeRF tree).  The
- * Python mirror in lush_nerf_amd/ binds these with ctypes and wraps them in
+ * Python mirror in lush_nerf_amd/ READS THIS FILE (abi.py: prototypes, structs and
+ * #define LUSH_X <integer> constants; a declaration outside its typing rule is an
+ * error at import), binds them with ctypes and wraps them in
  * torch.autograd.Function objects that keep the reference signatures.
  *
  * Conventions
@@ -28,7 +30,8 @@ extern "C" {
 typedef void* lush_stream_t;
 
 const char* lush_last_error(void);
-int lush_abi_version(void);   /* 10 (round 5; 9: lush_rbk_mlp_bwd consumes its d_rvw rows; 10: the live-point entry points lush_live_compact /
+#define LUSH_ABI_VERSION 10
+int lush_abi_version(void);   /* LUSH_ABI_VERSION of the library that was built: 10 (round 5; 9: lush_rbk_mlp_bwd consumes its d_rvw rows; 10: the live-point entry points lush_live_compact /
                              * lush_mlp_fwd_live / lush_mlp_bwd_*_live / lush_ray_grad_reduce_live, LUSH_VARIANT_DENSE_BWD,
                              * LUSH_VIEW_LIVE_COUNTS; the march's one- and two-plane backward runs on the live points).  Earlier: 8 (round 3: explicit kernel-variant argument instead of environment switches; 6: the blur-mix / tone-map
                              * backward entry points write their outputs instead of accumulating; 7, round 4: the fused ray-level
@@ -259,6 +262,7 @@ int lush_draws(unsigned long long seed, unsigned long long offset, float* t_rand
  * models/lushnerf.py:234-293).
  * net 0 = NeRF (D=8, W=256, skip after layer 4), net 1 = NeRF_Noise (D=4, W=128).
  * planes = bf16 planes per operand: 1 plain bf16, 2 parity mode (~2^-17), 3 ~fp32. */
+#define LUSH_PLANES_F16 17           /* ... or this plane code: ONE fp16 plane per operand */
 typedef struct lush_mlp_params {
     const float* w[8];
     const float* b[8];

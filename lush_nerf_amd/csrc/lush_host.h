@@ -4,9 +4,6 @@
 #include <atomic>
 #include "lush_mlp.h"
 
-struct lush_mlp_params;      // include/lush_march.h
-struct lush_mlp_grads;
-
 namespace lush {
 
 int set_error(const char* msg);                 // stores a thread-local message, returns -1

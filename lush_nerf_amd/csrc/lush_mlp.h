@@ -10,15 +10,12 @@
 // so a wave fetches one fragment with one fully coalesced 1-KiB load.
 #pragma once
 #include <stdint.h>
+#include "../../include/lush_march.h"      // the plane codes and the LUSH_VARIANT_* bits are stated there, once
 
 namespace lush {
 
 enum { NET_MAX_LAYERS = 8 };
-enum { PLANES_F16 = 17 };   // plane code: 1..3 = bf16 planes, 17 = ONE fp16 plane (forward of the NeRF nets)
-// kernel-variant bits of the C ABI (include/lush_march.h LUSH_VARIANT_*): 0 = the product's choice
-enum { LUSH_VARIANT_FWD_HALF = 1, LUSH_VARIANT_FWD_512 = 2, LUSH_VARIANT_BWD_512 = 4, LUSH_VARIANT_HEAD_KERNEL = 8, LUSH_VARIANT_BWD_HALF = 16,
-       LUSH_VARIANT_PE_ROWS = 64, LUSH_VARIANT_DW_SPLIT = 128, LUSH_VARIANT_DENSE_BWD = 256, LUSH_VARIANT_DW_WALK = 512,
-       LUSH_VARIANT_KERNEL_BITS = 0x3DF };
+constexpr int PLANES_F16 = LUSH_PLANES_F16;   // plane code: 1..3 = bf16 planes, 17 = ONE fp16 plane (forward of the NeRF nets)
 
 template <int HW_, int NL_, int SKIP_>
 struct NetT {

@@ -2,7 +2,7 @@
 
 The shared object is built IN-TREE by ``build()`` (hipcc --offload-arch=gfx950)
 and loaded with ctypes.  There is no fallback: if the library is missing or a
-call fails the product raises.  Signatures mirror include/lush_march.h.
+call fails the product raises.  Signatures, structs and constants are read from include/lush_march.h (abi.py).
 """
 from __future__ import annotations
 
@@ -10,6 +10,8 @@ import ctypes as C
 import os
 import subprocess
 from typing import Sequence
+
+from . import abi
 
 HERE = os.path.dirname(os.path.abspath(__file__))
 CSRC = os.path.join(HERE, "csrc")
@@ -110,127 +112,23 @@ def build(force: bool = False, verbose: bool = False, extra_flags: Sequence[str]
 LAST_BUILD_USAGE = {}
 
 
-class MlpParams(C.Structure):
-    _fields_ = [("w", C.c_void_p * 8), ("b", C.c_void_p * 8)] + \
-        [(n, C.c_void_p) for n in ("w_feat", "b_feat", "w_alpha", "b_alpha", "w_views", "b_views",
-                                   "w_rgb", "b_rgb")]
-
-
-class RbkParams(C.Structure):
-    _fields_ = [("embed", C.c_void_p), ("w_trunk", C.c_void_p * 4), ("b_trunk", C.c_void_p * 4)] + \
-        [(n, C.c_void_p) for n in ("w_rb", "b_rb", "w_vb", "b_vb", "w_wb", "b_wb", "w_r", "b_r",
-                                   "w_v", "b_v", "w_w", "b_w")]
-
-
-class MarchCfgC(C.Structure):       # include/lush_march.h: lush_march_cfg
-    _fields_ = [("R", C.c_int), ("N_samples", C.c_int), ("N_importance", C.c_int), ("perturb", C.c_float),
-                ("raw_noise_std", C.c_float), ("white_bkgd", C.c_int), ("lindisp", C.c_int), ("near_mask", C.c_float),
-                ("planes_fwd", C.c_int), ("planes_bwd", C.c_int), ("variant", C.c_int), ("same_net", C.c_int),
-                ("packed_coarse", C.c_void_p), ("packed_fine", C.c_void_p), ("packed_bwd_coarse", C.c_void_p),
-                ("packed_bwd_fine", C.c_void_p)]
-
-
-class PackJobC(C.Structure):        # include/lush_march.h: lush_pack_job
-    _fields_ = [("net", C.c_int), ("planes", C.c_int), ("variant", C.c_int), ("prm", C.POINTER(MlpParams)), ("packed", C.c_void_p)]
-
-
-class MarchDraws(C.Structure):
-    _fields_ = [(n, C.c_void_p) for n in ("t_rand", "noise_c", "u", "noise_f")]
-
-
-class MarchOut(C.Structure):
-    _fields_ = [(n, C.c_void_p) for n in ("rgb", "depth", "acc", "density", "rgb0", "depth0", "acc0", "density0", "z_std")]
-
-
-class MarchGout(C.Structure):
-    _fields_ = [(n, C.c_void_p) for n in ("rgb", "depth", "acc", "rgb0", "depth0", "acc0")]
-
-
-VIEW_Z, VIEW_RAW, VIEW_WEIGHTS, VIEW_Z_COARSE, VIEW_STASH_COARSE, VIEW_STASH_FINE, VIEW_LIVE_COUNTS = range(7)
-
-_p, _i, _f, _ll, _sz = C.c_void_p, C.c_int, C.c_float, C.c_longlong, C.c_size_t
-_SIGS = {
-    "lush_abi_version": ([], _i),
-    "lush_zgrid": ([_p, _i, _i, _i, _p, _p, _p], _i),
-    "lush_zfixed": ([_p, _i, _i, _i, _i, _p, _p], _i),
-    "lush_composite_fwd": ([_p, _p, _p, _i, _i, _p, _f, _f, _i, _p, _p, _p, _p, _p, _p, _i, _p], _i),
-    "lush_composite_bwd": ([_p, _p, _p, _i, _i, _p, _f, _f, _i, _p, _p, _p, _p, _p, _p, _p, _ll, _i, _p], _i),
-    "lush_composite_bwd_blocks": ([_i], _i),
-    "lush_composite_bwd_full": ([_p, _p, _p, _i, _i, _p, _f, _f, _i, _p, _p, _p, _p, _p, _p, _p, _p, _p], _i),
-    "lush_loss_scale": ([_p, _i, _p, _p], _i),
-    "lush_sample_merge": ([_p, _p, _i, _i, _i, _p, _p, _p, _p, _p, _p], _i),
-    "lush_pack_rays_fwd": ([_p, _i, _i, _f, _f, _f, _f, _p, _p], _i),
-    "lush_pack_rays_bwd": ([_p, _i, _i, _f, _f, _p, _p, _p], _i),
-    "lush_gen_rays": ([_p, _p, _p, _p, _i, _f, _f, _f, _f, _p, _p], _i),
-    "lush_gen_rays_image": ([_p, _i, _i, _f, _f, _f, _f, _p, _p], _i),
-    "lush_align_rays": ([_p, _p, _p, _i, _p, _i, _i, _ll, _i, _i, _f, _f, _f, _f, _p, _p, _p], _i),
-    "lush_consist_loss_fwd_bwd": ([_p, _p, _i, _i, _f, _p, _p, _p], _i),
-    "lush_rbk_mlp_fwd": ([C.POINTER(RbkParams), _i, _i, _f, _p, _p], _i),
-    "lush_rbk_mlp_bwd": ([C.POINTER(RbkParams), _i, _i, _f, _p, _p, _i, C.POINTER(RbkParams), _p, _i, _p], _i),
-    "lush_rbk_warp_fwd": ([_p, _p, _i, _i, _p, _p, _p, _p], _i),
-    "lush_rbk_warp_bwd": ([_p, _p, _i, _i, _p, _p, _p, _p, _p, _i, _p, _p], _i),
-    "lush_rbk_warp_ndc_fwd": ([_p, _p, _i, _i, _p, _i, _f, _f, _f, _f, _p, _p, _p, _p], _i),
-    "lush_rbk_warp_ndc_bwd": ([_p, _p, _i, _i, _p, _i, _f, _f, _p, _p, _p, _p, _i, _p, _i, _p], _i),
-    "lush_blur_mix_fwd": ([_p, _p, _p, _p, _i, _i, _i, _i, _p, _p, _p, _p, _p, _p], _i),
-    "lush_blur_mix_bwd": ([_p, _p, _p, _p, _i, _i, _i, _i, _p, _p, _p, _p, _p, _p, _p, _p, _p, _p], _i),
-    "lush_wsum_fwd": ([_p, _p, _i, _i, _i, _p, _p], _i),
-    "lush_wsum_bwd": ([_p, _p, _i, _i, _i, _p, _p, _p, _p], _i),
-    "lush_tonemap_fwd": ([_p, _p, _i, _i, _p, _p], _i),
-    "lush_tonemap_bwd": ([_p, _p, _i, _i, _p, _p, _p, _p], _i),
-    "lush_noise_act_fwd": ([_p, _i, _p, _p], _i),
-    "lush_noise_act_bwd": ([_p, _i, _p, _p, _p], _i),
-    "lush_loss_fwd_bwd": ([_p, _p, _p, _i, _f, _p, _p, _p, _p, _p], _i),
-    "lush_draws": ([C.c_ulonglong, C.c_ulonglong, _p, _ll, _p, _ll, _p, _ll, _p, _ll, _p], _i),
-    "lush_mlp_packed_bytes": ([_i, _i], _sz),
-    "lush_pack_plan_bytes": ([_i], _sz),
-    "lush_pack_plan_build": ([_p, _i, _p, _sz, _p], _i),
-    "lush_pack_plan_run": ([_p, _i, _p, _ll, _p], _i),
-    "lush_mlp_pack": ([_i, _i, C.POINTER(MlpParams), _p, _p], _i),
-    "lush_mlp_pack_for": ([_i, _i, C.POINTER(MlpParams), _p, _i, _p], _i),
-    "lush_mlp_stash_bytes": ([_i, _i, _i, _ll], _sz),
-    "lush_mlp_dstash_bytes": ([_i, _i, _ll], _sz),
-    "lush_mlp_fwd": ([_i, _i, _i, _p, _p, _i, _i, _p, C.POINTER(MlpParams), _p, _p, _i, _p], _i),
-    "lush_mlp_bwd": ([_i, _i, _i, _p, _p, _i, _i, _p, C.POINTER(MlpParams), _p, _p, _p,
-                      C.POINTER(MlpParams), _p, _i, _p], _i),
-    "lush_mlp_bwd_chain": ([_i, _i, _i, _p, _p, _i, _i, _p, C.POINTER(MlpParams), _p, _p, _p, _p, _i, _p], _i),
-    "lush_mlp_bwd_weights": ([_i, _i, _i, _i, _i, C.POINTER(MlpParams), _p, _p, _p, C.POINTER(MlpParams), _i, _p], _i),
-    "lush_ray_grad_reduce": ([_p, _p, _i, _i, _p, _p], _i),
-    "lush_points_pack": ([_p, _p, _i, _i, _p, _p, _p], _i),
-    "lush_points_grad": ([_p, _i, _i, _p, _p, _p], _i),
-    "lush_live_aux_bytes": ([_ll], _sz),
-    "lush_live_compact": ([_p, _i, _i, _p, _p, _p, _p, _p, _p], _i),
-    "lush_mlp_fwd_live": ([_i, _i, _i, _p, _p, _i, _i, _p, C.POINTER(MlpParams), _p, _p, _p, _i, _p], _i),
-    "lush_mlp_bwd_chain_live": ([_i, _i, _i, _p, _p, _i, _i, _p, C.POINTER(MlpParams), _p, _p, _p, _p, _p, _p, _i, _p], _i),
-    "lush_mlp_bwd_weights_live": ([_i, _i, _i, _i, _i, C.POINTER(MlpParams), _p, _p, _p, C.POINTER(MlpParams), _p, _i, _p], _i),
-    "lush_ray_grad_reduce_live": ([_p, _p, _p, _p, _i, _p, _p], _i),
-    "lush_march_workspace_bytes": ([C.POINTER(MarchCfgC)], _sz),
-    "lush_march_view": ([C.POINTER(MarchCfgC), _i, C.POINTER(_sz), C.POINTER(_sz)], _i),
-    "lush_march_fwd": ([C.POINTER(MarchCfgC), _p, C.POINTER(MlpParams), C.POINTER(MlpParams), C.POINTER(MarchDraws),
-                        C.POINTER(MarchOut), _p, _p, _p], _i),
-    "lush_march_bwd": ([C.POINTER(MarchCfgC), _p, C.POINTER(MlpParams), C.POINTER(MlpParams), C.POINTER(MarchDraws),
-                        C.POINTER(MarchGout), _p, C.POINTER(MlpParams), C.POINTER(MlpParams), _p, _p], _i),
-    "lush_adam": ([_p, _p, _p, _p, _ll, _f, _f, _f, _f, _i, _f, _p], _i),
-    "lush_step_state_bytes": ([], _sz),
-    "lush_step_state_init": ([_p, C.c_ulonglong, _i, C.POINTER(_i), C.c_double, C.c_double, C.c_double, C.c_double, _p], _i),
-    "lush_step_state_advance": ([_p, _i, _i, C.c_double, C.c_double, C.c_double, C.c_double, _p], _i),
-    "lush_draws_state": ([C.c_ulonglong, C.c_ulonglong, _p, _p, _ll, _p, _ll, _p, _ll, _p, _ll, _p], _i),
-    "lush_adam_state": ([_p, _p, _p, _p, _ll, _p, _i, _f, _f, _f, _f, _p], _i),
-    "lush_adam_multi": ([_p, _p, _p, _p, _ll, _ll, _ll, _i, _f, _f, _f, _f, _p, _f, _p], _i),
-    "lush_adam_state_multi": ([_p, _p, _p, _p, _ll, _ll, _ll, _p, _i, _f, _f, _f, _f, _p], _i),
-    "lush_debug_stash_layout": ([_i, _i, _ll, C.POINTER(_ll)], _i),
-    "lush_debug_dw_plan": ([_i, _i, _i, _ll, _i, _i, _i, C.POINTER(_ll)], _i),
-}
-EXPORTS = ["lush_last_error"] + list(_SIGS)
-ABI_VERSION = 10
-PLANES_F16 = 17          # include/lush_march.h: plane code of ONE fp16 plane (1..3 = bf16 planes)
-# include/lush_march.h: LUSH_VARIANT_* (kernel-variant bits of the MLP entry points; 0 = the product's choice)
-VARIANT_FWD_HALF, VARIANT_FWD_512, VARIANT_BWD_512, VARIANT_HEAD_KERNEL, VARIANT_BWD_HALF, VARIANT_PE_ROWS, VARIANT_DW_SPLIT, VARIANT_DENSE_BWD = 1, 2, 4, 8, 16, 64, 128, 256
-VARIANT_DW_WALK = 512
-# include/lush_march.h: LUSH_FAULT_*
-FAULT_NAMES = {1: "rgb_map", 2: "depth_map", 4: "acc_map", 8: "density_map", 16: "raw", 32: "rgb0", 64: "depth0",
-               128: "acc0", 256: "density0", 512: "raw0", 1024: "z_std"}
+# The binding is READ from the header (abi.py): signatures, structs and constants are stated there, once.
+_abi = abi.parse(open(os.path.join(CSRC, HEADERS[-1])).read())
+_SIGS = _abi.protos                     # name -> (argtypes, restype), every prototype of the header
+EXPORTS = list(_SIGS)
+MlpParams, RbkParams = _abi.structs["lush_mlp_params"], _abi.structs["lush_rbk_params"]      # ... and lush_mlp_grads / lush_rbk_grads
+MarchCfgC, PackJobC = _abi.structs["lush_march_cfg"], _abi.structs["lush_pack_job"]
+MarchDraws, MarchOut, MarchGout = (_abi.structs["lush_march_" + n] for n in ("draws", "out", "gout"))
+# every LUSH_X of the header as lib.X: ABI_VERSION, PLANES_F16 (plane code of ONE fp16 plane; 1..3 = bf16 planes), VARIANT_* (kernel-variant
+# bits of the MLP entry points; 0 = the product's choice), VIEW_*, FAULT_*, RBK_*
+globals().update({k[len("LUSH_"):]: v for k, v in _abi.consts.items()})
+# bits of the numerical-fault word -> keys of the render result dict (final pass, coarse pass)
+_FAULT_KEYS = {"RGB": ("rgb_map", "rgb0"), "DEPTH": ("depth_map", "depth0"), "ACC": ("acc_map", "acc0"),
+               "DENSITY": ("density_map", "density0"), "RAW": ("raw", "raw0")}
+FAULT_NAMES = {_abi.consts["LUSH_FAULT_" + c] << shift: keys[k]
+               for k, shift in enumerate((0, _abi.consts["LUSH_FAULT_COARSE_SHIFT"])) for c, keys in _FAULT_KEYS.items()}
+FAULT_NAMES[_abi.consts["LUSH_FAULT_ZSTD"]] = "z_std"
 FAULT_BITS = {n: b for b, n in FAULT_NAMES.items()}
-FAULT_COARSE_SHIFT = 5
 
 
 def fault_names(word: int):
@@ -249,8 +147,6 @@ def load():
         raise RuntimeError(f"{SO_PATH} is missing: run `python -c 'import __graft_entry__ as g; g.build()'` "
                            "(the HIP extension is required; there is no fallback path)")
     lib = C.CDLL(SO_PATH)
-    lib.lush_last_error.argtypes = []
-    lib.lush_last_error.restype = C.c_char_p
     for name, (args, res) in _SIGS.items():
         fn = getattr(lib, name)
         fn.argtypes = args

@@ -15,7 +15,7 @@ import torch
 from . import lib
 
 NET_NERF, NET_NOISE = 0, 1
-PLANES_F16 = 17          # plane code of the C ABI: 1..3 = bf16 planes, 17 = ONE fp16 plane (forward only)
+PLANES_F16 = lib.PLANES_F16          # plane code of the C ABI: 1..3 = bf16 planes, this one = ONE fp16 plane
 
 
 def nplanes(code: int) -> int:
@@ -807,9 +807,7 @@ class Composite(torch.autograd.Function):
 
 
 # ----------------------------------------------------------------------------- blur kernel
-RBK_ACT = 512
-RBK_RVW = 32
-RBK_RVW_OFFSET = 480     # include/lush_march.h LUSH_RBK_RVW_OFFSET
+RBK_ACT, RBK_RVW_OFFSET = lib.RBK_ACT_STRIDE, lib.RBK_RVW_OFFSET      # include/lush_march.h LUSH_RBK_*
 
 
 class RbkWarp(torch.autograd.Function):

@@ -25,8 +25,9 @@ def test_library_builds_and_exports_every_declared_symbol():
     assert len(declared) >= 30
     missing = [n for n in sorted(declared) if not hasattr(so, n)]
     assert not missing, missing
-    assert set(lib.EXPORTS) <= declared | {"lush_last_error"}
+    assert set(lib.EXPORTS) == declared      # nothing is bound that is not declared, nothing declared is left unbound
     l = lib.load()
+    assert all(list(getattr(l, n).argtypes) == lib._SIGS[n][0] and getattr(l, n).restype is lib._SIGS[n][1] for n in declared)
     assert l.lush_abi_version() == lib.ABI_VERSION == 10
     # pure host queries (no device work)
     p1, p3 = l.lush_mlp_packed_bytes(0, 1), l.lush_mlp_packed_bytes(0, 3)
@@ -34,6 +35,107 @@ def test_library_builds_and_exports_every_declared_symbol():
     assert l.lush_mlp_packed_bytes(7, 1) == 0
     assert l.lush_mlp_stash_bytes(0, 2, 2, 64) > 0 and l.lush_mlp_stash_bytes(0, 2, 1, 65) == l.lush_mlp_stash_bytes(0, 2, 1, 128)
     assert 0 < l.lush_mlp_stash_bytes(0, 2, 0, 128) < l.lush_mlp_stash_bytes(0, 2, 1, 128) < l.lush_mlp_stash_bytes(0, 2, 2, 128)
+
+
+def _pinned_abi():
+    import json
+    return json.load(open(os.path.join(ROOT, "tests", "abi_signatures.json")))
+
+
+def test_binding_read_from_the_header_is_the_hand_written_one():
+    """lib.py binds what abi.py reads from include/lush_march.h.  tests/abi_signatures.json is the table, the constants and the
+    struct layouts that lib.py and ops.py stated by hand before that (dumped from them, letter by letter): the derived binding
+    equals it entry for entry -- the hand-written POINTER(c_size_t / c_longlong / c_int) of host out-parameters count as `p`, and
+    the `jobs` of lush_pack_plan_build is the one struct pointer the table had left untyped."""
+    pin = _pinned_abi()
+    a = lib._abi                             # abi.parse(include/lush_march.h), read once at import
+    assert (len(a.protos), len(a.structs), len(a.consts)) == (67, 9, 29)
+    assert a.protos is lib._SIGS and list(a.protos) == lib.EXPORTS
+    kind = {"i": ctypes.c_int, "f": ctypes.c_float, "d": ctypes.c_double, "ll": ctypes.c_longlong, "ull": ctypes.c_ulonglong,
+            "sz": ctypes.c_size_t, "p": ctypes.c_void_p, "str": ctypes.c_char_p}
+    kind.update({n: ctypes.POINTER(c) for n, c in a.structs.items()})
+    assert set(a.protos) == set(pin["prototypes"])
+    # ONE entry is typed where the hand-written table had a plain `p`: `const lush_pack_job* jobs` is a pointer to a struct of the
+    # header.  Its only caller (ops.PackPlan) passes a PackJobC array, which the typed pointer takes; a float or a tensor address no longer passes
+    assert pin["prototypes"]["lush_pack_plan_build"][0][0] == "p"
+    pin["prototypes"]["lush_pack_plan_build"][0][0] = "lush_pack_job"
+    ctypes.POINTER(lib.PackJobC).from_param((lib.PackJobC * 2)())
+    for name, (args, res) in pin["prototypes"].items():
+        got_args, got_res = a.protos[name]
+        assert len(got_args) == len(args) and all(g is kind[k] for g, k in zip(got_args, args)), name
+        assert got_res is kind[res], name
+    # constants: the literals lib.py / ops.py carried (and the three only the header and csrc/ had), under the public names
+    want = {**pin["constants"], **pin["constants_header_only"]}
+    assert a.consts == want and len(pin["constants_header_only"]) == 3
+    assert all(getattr(lib, k[len("LUSH_"):]) == v for k, v in want.items())
+    assert lib.FAULT_NAMES == {int(b): n for b, n in pin["fault_names"].items()} and list(lib.FAULT_NAMES) == sorted(lib.FAULT_NAMES)
+    from lush_nerf_amd import ops
+    assert ops.PLANES_F16 == lib.PLANES_F16 == 17 and ops.RBK_RVW_OFFSET == lib.RBK_RVW_OFFSET == 480
+
+
+def test_structs_read_from_the_header_have_the_hand_written_layout():
+    """Each of the header's 9 structs: field names in header order, sizeof and every field's offset and size as the hand-written
+    classes had them (tests/abi_signatures.json); a *_grads struct and its *_params twin differ in `const` alone and are ONE class,
+    so lib.mlp_struct / rbk_struct serve both roles and byref() of one is accepted for either pointer type."""
+    pin = _pinned_abi()
+    structs = lib._abi.structs
+    assert list(structs) == list(pin["structs"]) and len(structs) == 9
+    for name, want in pin["structs"].items():
+        cls = structs[name]
+        assert ctypes.sizeof(cls) == want["size"], name
+        assert [[f[0], getattr(cls, f[0]).offset, getattr(cls, f[0]).size] for f in cls._fields_] == want["fields"], name
+    for a, b in pin["aliases"]:
+        assert structs[a] is structs[b], (a, b)
+    assert len(set(structs.values())) == 7
+    assert (lib.MlpParams, lib.RbkParams, lib.MarchCfgC, lib.PackJobC, lib.MarchDraws, lib.MarchOut, lib.MarchGout) == tuple(
+        structs[n] for n in ("lush_mlp_grads", "lush_rbk_grads", "lush_march_cfg", "lush_pack_job", "lush_march_draws", "lush_march_out", "lush_march_gout"))
+    assert lib.PackJobC.prm.size == 8 and dict(lib.PackJobC._fields_)["prm"] is ctypes.POINTER(lib.MlpParams)
+
+
+def test_header_reader_refuses_rather_than_guesses():
+    """abi.parse on small header strings: what the typing rule does not cover raises and names the declaration; comments inside a
+    parameter list and several declarators on one struct line are read."""
+    from lush_nerf_amd import abi
+    for text, word in (("int lush_f(int n, uint8_t flag, lush_stream_t s);", "lush_f"),               # unknown parameter type
+                       ("int lush_f(float** rows);", "lush_f"),
+                       ("float* lush_f(int n);", "lush_f"),
+                       ("#define LUSH_SCALE 1.5f\n", "LUSH_SCALE"),
+                       ("#define LUSH_BOTH (LUSH_A | LUSH_B)\n", "LUSH_BOTH"),
+                       ("#define LUSH_MAX(a, b) ((a) > (b) ? (a) : (b))\n", "LUSH_MAX"),
+                       ("typedef struct { int n; short tag; } lush_s;", "lush_s"),                    # unknown field type
+                       ("typedef struct { int n; float m[2][2]; } lush_s;", "lush_s"),
+                       ("typedef int lush_handle;", "lush_handle"),
+                       ("extern int lush_counter;", "lush_counter")):
+        with pytest.raises(ValueError, match=word):
+            abi.parse(text)
+    a = abi.parse('''/* a header */
+#ifndef LUSH_T_H
+#define LUSH_T_H
+#ifdef __cplusplus
+extern "C" {
+#endif
+typedef void* lush_stream_t;
+#define LUSH_A 7      /* a comment that goes on
+#define LUSH_GONE 1
+                       * over several lines */
+#define LUSH_B 0x1F
+typedef struct lush_p { const float* w[8]; const float *w_rb, *b_rb; int n, m; float x; } lush_p;
+typedef struct { float* w[8]; float *w_rb, *b_rb; int n, m; float x; } lush_g;
+const char* lush_why(void);
+size_t lush_f(void* state, const int* adam_steps /* host, 3 */, const lush_g* g, unsigned long long seed,   // trailing
+              long long n, double lr, size_t* bytes, lush_stream_t stream);
+#ifdef __cplusplus
+}
+#endif
+#endif
+''')
+    assert a.consts == {"LUSH_A": 7, "LUSH_B": 31}
+    P = a.structs["lush_p"]
+    assert a.structs["lush_g"] is P and [f[0] for f in P._fields_] == ["w", "w_rb", "b_rb", "n", "m", "x"]
+    assert [f[1] for f in P._fields_] == [ctypes.c_void_p * 8, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_int, ctypes.c_int, ctypes.c_float]
+    v = ctypes.c_void_p
+    assert a.protos == {"lush_why": ([], ctypes.c_char_p),
+                        "lush_f": ([v, v, ctypes.POINTER(P), ctypes.c_ulonglong, ctypes.c_longlong, ctypes.c_double, v, v], ctypes.c_size_t)}
 
 
 def test_product_refuses_cpu_tensors():
