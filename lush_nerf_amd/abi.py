@@ -15,8 +15,9 @@ _INT = r"0[xX][0-9a-fA-F]+|0|[1-9][0-9]*"
 _DECL = r"(\*?)\s*(\w+)\s*(?:\[(\d+)\])?"      # [*] name [N]
 
 
-def parse(text: str) -> SimpleNamespace:
-    """consts {LUSH_X: int}, structs {header name: ctypes.Structure class}, protos {lush_name: (argtypes, restype)}."""
+def parse(text: str, header: str = "lush_march.h") -> SimpleNamespace:
+    """consts {LUSH_X: int}, structs {header name: ctypes.Structure class}, protos {lush_name: (argtypes, restype)}.
+    `header` names the file being read, for the error messages."""
     text = re.sub(r"/\*.*?\*/|//[^\n]*", " ", text, flags=re.S)
     consts, structs, protos, classes = {}, {}, {}, {}
 
@@ -27,13 +28,13 @@ def parse(text: str) -> SimpleNamespace:
         if star:
             return C.POINTER(structs[base]) if base in structs else C.c_void_p
         if base not in _SCALARS:
-            raise ValueError(f"lush_march.h: unknown type `{base}` in `{where}`")
+            raise ValueError(f"{header}: unknown type `{base}` in `{where}`")
         return _SCALARS[base]
 
     for name, body in re.findall(r"^[ \t]*#[ \t]*define[ \t]+(LUSH_\w+)(.*)$", text, flags=re.M):
         if body.strip():      # (an empty body is the include guard)
             if not re.fullmatch(_INT, body.strip()):
-                raise ValueError(f"lush_march.h: `#define {name}{body}` is not an integer constant")
+                raise ValueError(f"{header}: `#define {name}{body}` is not an integer constant")
             consts[name] = int(body.strip(), 0)
     text = re.sub(r"^[ \t]*#.*$", "", text, flags=re.M)
     text, n_extern = re.subn(r'extern\s+"C"\s*\{', "", text)
@@ -47,7 +48,7 @@ def parse(text: str) -> SimpleNamespace:
             head = re.fullmatch(r"(\w[\w\s]*?)\s*" + _DECL, first.strip())
             rest = [re.fullmatch(_DECL, d.strip()) for d in more]
             if not head or not all(rest):
-                raise ValueError(f"lush_march.h: cannot read the field `{decl}` of {m.group(2)}")
+                raise ValueError(f"{header}: cannot read the field `{decl}` of {m.group(2)}")
             for star, field, count in [head.groups()[1:]] + [r.groups() for r in rest]:
                 t = ctype(head.group(1), star, f"{decl}` of `{m.group(2)}")
                 fields.append((field, t * int(count) if count else t))
@@ -64,13 +65,13 @@ def parse(text: str) -> SimpleNamespace:
             continue
         m = re.fullmatch(r"(\w[\w\s]*?\s*\*?)\s*\b(lush_\w+)\s*\((.*)\)", stmt)
         if not m:
-            raise ValueError(f"lush_march.h: cannot read the declaration `{stmt}`")
+            raise ValueError(f"{header}: cannot read the declaration `{stmt}`")
         ret, name, args = m.groups()
         argtypes = []
         for arg in ([] if args.strip() == "void" else args.split(",")):
             a = re.fullmatch(r"(\w[\w\s]*?)\s*(\*?)\s*(\w+)", arg.strip())
             if not a:
-                raise ValueError(f"lush_march.h: cannot read the parameter `{arg.strip()}` of `{stmt}`")
+                raise ValueError(f"{header}: cannot read the parameter `{arg.strip()}` of `{stmt}`")
             argtypes.append(ctype(a.group(1), a.group(2), stmt))
         is_str = re.sub(r"\s", "", ret) == "constchar*"
         protos[name] = (argtypes, C.c_char_p if is_str else ctype(ret, "", stmt))

@@ -6,6 +6,7 @@
 #include "lush_composite.h"
 #include <type_traits>
 #include "../../include/lush_march.h"
+#include "../../include/lush_subframe.h"
 
 #include <cmath>
 #include <string>
@@ -724,6 +725,48 @@ __global__ void rbk_warp_ndc_fwd_kernel(const float* __restrict__ rays, const in
     pack_one(oo, dd, ndc, cx, cy, near, far, batch + t * 11);
     ccw[t] = A[RA_WN + m];
     if (m == 0 && batch0 != nullptr) pack_one(oo, dd, ndc, cx, cy, near, far, batch0 + n * 11);
+}
+
+// The same for every pixel of ONE training view, rows sub-frame-major (NeRFAll.render_warped_path, models/lushnerf.py:898-947: get_rays
+// :917, mlp_rbk :921-925, the head of render_train_scene :929): c2w [3][4], image_idx [1] (read here: no host read-back) ->
+// batch [(M+1)*H*W][11] with row m*H*W + n = sub-frame m of pixel n, centre_rays [M+1][3][2] = the un-packed warped rays of pixel
+// (H/2, W/2) (:926; may be NULL).  One thread per (sub-frame, pixel), consecutive threads on consecutive pixels of one sub-frame:
+// neither the ray table nor the warped rays exist in memory, and the march's outputs are [M+1][H][W] images as they stand.
+// The pixel's ray is gen_rays_image_kernel's expression, the warp rbk_warp_ndc_fwd_kernel's: the rows have the same bits.
+__global__ __launch_bounds__(256) void warp_image_fwd_kernel(const float* __restrict__ c2w, int H, int W, float fx, float fy, float kx,
+                                        float ky, const int64_t* __restrict__ image_idx, int num_img, int M,
+                                        const float* __restrict__ acts, int ndc, float cx, float cy, float near, float far,
+                                        float* __restrict__ batch, float* __restrict__ centre_rays) {
+    const long long t = (long long)blockIdx.x * blockDim.x + threadIdx.x;
+    const long long HW = (long long)H * W;
+    if (t >= HW * (M + 1)) return;
+    const int m = (int)(t / HW);
+    const long long n = t % HW;
+    const int px = (int)(n % W), py = (int)(n / W);
+    const float d0 = ((float)px + (0.5f - kx)) / fx;
+    const float d1 = -((float)py + (0.5f - ky)) / fy;
+    const float d2 = -1.f;
+    const V3 o = {c2w[3], c2w[7], c2w[11]};
+    const V3 d = {(d0 * c2w[0] + d1 * c2w[1]) + d2 * c2w[2], (d0 * c2w[4] + d1 * c2w[5]) + d2 * c2w[6],
+                  (d0 * c2w[8] + d1 * c2w[9]) + d2 * c2w[10]};
+    long long img = image_idx[0];
+    img = img < 0 ? 0 : (img >= num_img ? num_img - 1 : img);     // memory safety only: the reference would raise an IndexError
+    const float* A = acts + img * LUSH_RBK_ACT_STRIDE;
+    V3 wo = o, wd = d;
+    if (m > 0) {    // r.reshape(N,3,M): component c of motion m-1 is column c*M + m-1 (models/lushnerf.py:76)
+        const int k = m - 1;
+        const V3 r = {A[RA_R + k], A[RA_R + M + k], A[RA_R + 2 * M + k]};
+        const V3 v = {A[RA_V + k], A[RA_V + M + k], A[RA_V + 2 * M + k]};
+        const Se3 q = se3_setup(r, v);
+        wo = se3_apply(q, o);
+        wd = se3_apply(q, o + d) - wo;
+    }
+    const float oo[3] = {wo.x, wo.y, wo.z}, dd[3] = {wd.x, wd.y, wd.z};
+    pack_one(oo, dd, ndc, cx, cy, near, far, batch + t * 11);
+    if (centre_rays != nullptr && py == H / 2 && px == W / 2) {
+        float* c6 = centre_rays + m * 6;
+        c6[0] = wo.x; c6[1] = wd.x; c6[2] = wo.y; c6[3] = wd.y; c6[4] = wo.z; c6[5] = wd.z;
+    }
 }
 
 // Reverse: dbatch [N*(M+1)][11] (may be NULL: only the weights' gradient), dccw [N][M+1] (may be NULL) -> d_rvw [num_img][stride]
@@ -1742,6 +1785,20 @@ int lush_rbk_warp_ndc_fwd(const float* rays, const int64_t* idx, int N, int M, c
     if (!rays || !idx || !acts || !batch || !ccw) return set_error("lush_rbk_warp_ndc_fwd: rays, idx, acts, batch and ccw are required");
     hipLaunchKernelGGL(rbk_warp_ndc_fwd_kernel, dim3(cdiv((long long)N * (M + 1), 256)), dim3(256), 0, S_(st), rays, idx, N, M, acts, ndc,
                        cx, cy, near, far, batch, ccw, batch0);
+    CHECK_LAUNCH();
+    return 0;
+}
+int lush_warp_image_fwd(const float* c2w, int H, int W, float fx, float fy, float kx, float ky, const int64_t* image_idx, int num_img,
+                        int M, const float* acts, int ndc, float cx, float cy, float near, float far, float* batch, float* centre_rays,
+                        lush_stream_t st) {
+    if (H <= 0 || W <= 0) return set_error("lush_warp_image_fwd: empty image");
+    if (M < 1 || M > 4) return set_error("lush_warp_image_fwd: 1 <= num_motion <= 4");
+    if (num_img < 1) return set_error("lush_warp_image_fwd: no images");
+    const long long rows = (long long)H * W * (M + 1);
+    if (rows > 0x7fffffffLL) return set_error("lush_warp_image_fwd: H*W*(num_motion+1) must stay below 2^31 (the march counts its rays in an int)");
+    if (!c2w || !image_idx || !acts || !batch) return set_error("lush_warp_image_fwd: c2w, image_idx, acts and batch are required");
+    hipLaunchKernelGGL(warp_image_fwd_kernel, dim3(cdiv(rows, 256)), dim3(256), 0, S_(st), c2w, H, W, fx, fy, kx, ky, image_idx, num_img, M,
+                       acts, ndc, cx, cy, near, far, batch, centre_rays);
     CHECK_LAUNCH();
     return 0;
 }

@@ -2,7 +2,8 @@
 
 The shared object is built IN-TREE by ``build()`` (hipcc --offload-arch=gfx950)
 and loaded with ctypes.  There is no fallback: if the library is missing or a
-call fails the product raises.  Signatures, structs and constants are read from include/lush_march.h (abi.py).
+call fails the product raises.  Signatures, structs and constants are read from include/lush_march.h (abi.py), the one
+later entry point from the second contract header include/lush_subframe.h.
 """
 from __future__ import annotations
 
@@ -17,7 +18,8 @@ HERE = os.path.dirname(os.path.abspath(__file__))
 CSRC = os.path.join(HERE, "csrc")
 SO_PATH = os.path.join(HERE, "liblush_march.so")      # (developer tools load another build with use_library(path) BEFORE load())
 SOURCES = ["lush_march.hip", "lush_mlp.hip", "lush_mlp_chain.hip", "lush_mlp_wide.hip", "lush_mlp_wide_bwd.hip", "lush_abi.hip", "lush_march_abi.hip", "lush_field.hip"]
-HEADERS = ["lush_common.h", "lush_composite.h", "lush_mlp.h", "lush_mlp_dev.h", "lush_mlp_wide.h", "lush_host.h", os.path.join("..", "..", "include", "lush_march.h")]
+HEADERS = ["lush_common.h", "lush_composite.h", "lush_mlp.h", "lush_mlp_dev.h", "lush_mlp_wide.h", "lush_host.h", os.path.join("..", "..", "include", "lush_subframe.h"),
+           os.path.join("..", "..", "include", "lush_march.h")]      # (the last one is the contract _abi is read from)
 
 _lib = None
 
@@ -129,6 +131,10 @@ FAULT_NAMES = {_abi.consts["LUSH_FAULT_" + c] << shift: keys[k]
                for k, shift in enumerate((0, _abi.consts["LUSH_FAULT_COARSE_SHIFT"])) for c, keys in _FAULT_KEYS.items()}
 FAULT_NAMES[_abi.consts["LUSH_FAULT_ZSTD"]] = "z_std"
 FAULT_BITS = {n: b for b, n in FAULT_NAMES.items()}
+# The second contract header, include/lush_subframe.h (one entry point of the same library; lush_march.h and its tables above stay as they are)
+_abi_subframe = abi.parse(open(os.path.join(CSRC, HEADERS[-2])).read(), "lush_subframe.h")
+_SIGS_SUBFRAME = _abi_subframe.protos
+EXPORTS_SUBFRAME = list(_SIGS_SUBFRAME)
 
 
 def fault_names(word: int):
@@ -147,7 +153,7 @@ def load():
         raise RuntimeError(f"{SO_PATH} is missing: run `python -c 'import __graft_entry__ as g; g.build()'` "
                            "(the HIP extension is required; there is no fallback path)")
     lib = C.CDLL(SO_PATH)
-    for name, (args, res) in _SIGS.items():
+    for name, (args, res) in (*_SIGS.items(), *_SIGS_SUBFRAME.items()):
         fn = getattr(lib, name)
         fn.argtypes = args
         fn.restype = res

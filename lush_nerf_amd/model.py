@@ -105,6 +105,13 @@ class Rigid_Blurring_Kernel(nn.Module):
         return ops.RbkWarpNdc.apply(rays, rays_info['images_idx'], self.num_motion, self.rv_window, grad_mask, hooks,
                                     H, W, focal, ndc, near, far, *self.tensors())
 
+    def warp_image(self, c2w, image_idx, H, W, K, ndc, near, far, acts=None, hooks=None):
+        """forward() for every pixel of one pose of view `image_idx`, followed by the same ray prologue, in one kernel
+        (ops.warp_image; forward only) -> (ray batch [(M+1)*H*W,11] with SUB-FRAME-MAJOR rows, the warped rays of the centre
+        pixel [M+1,3,2], acts).  `acts`: the third value of an earlier call (the network's output for every view), or None."""
+        return ops.warp_image(c2w, image_idx, H, W, K, ndc, near, far, self.num_motion, self.rv_window, hooks, *self.tensors(),
+                              acts=acts)
+
     def rbk_weighted_sum(self, rgb, depth, acc, extras, ccw):
         rgb, depth, acc = ops.WSum.apply(rgb, ccw), ops.WSum.apply(depth, ccw), ops.WSum.apply(acc, ccw)
         for k, v in extras.items():
@@ -349,12 +356,18 @@ class NeRFAll(nn.Module):
         k_extract = ['rgb_map', 'depth_map', 'acc_map']
         return [all_ret[k] for k in k_extract] + [{k: v for k, v in all_ret.items() if k not in k_extract}]
 
-    def _render_train_scene_packed(self, batch, chunk, draws=None, **kwargs):
-        """render_train_scene on an already packed ray batch [R,11] (the fused warp + NDC kernel made it)."""
+    def _render_train_scene_packed(self, batch, chunk, draws=None, keep=None, **kwargs):
+        """render_train_scene on an already packed ray batch [R,11] (the fused warp + NDC kernel made it).  `keep`: the keys of the
+        per-ray dict a caller of many chunks wants (rgb_map, depth_map and acc_map among them); the others are dropped chunk by
+        chunk instead of being concatenated over the whole image."""
         self._refuse_unbuilt(kwargs.get("c2w_staticcam"), kwargs.get("use_awp", False))
         for k in ("c2w", "ndc", "near", "far", "use_viewdirs", "c2w_staticcam", "use_awp", "allkernel", "kernelpixel", "render_noise"):
             kwargs.pop(k, None)
-        res = self._chunks(lambda b, d: self.render_rays_nonoise(b, draws=d, **kwargs), batch, chunk, draws)
+
+        def fn(b, d):
+            r = self.render_rays_nonoise(b, draws=d, **kwargs)
+            return r if keep is None else {k: r[k] for k in keep}
+        res = self._chunks(fn, batch, chunk, draws)
         all_ret = self._merge(res, batch.shape[:-1])
         k_extract = ['rgb_map', 'depth_map', 'acc_map']
         return [all_ret[k] for k in k_extract] + [{k: v for k, v in all_ret.items() if k not in k_extract}]
@@ -422,6 +435,43 @@ class NeRFAll(nn.Module):
                                                                      c2w=c2w[:3, :4], **render_kwargs)
             rgbs.append(rgb); depths.append(depth); noises.append(noise)
         return torch.stack(rgbs, 0), torch.stack(noises, 0), torch.stack(depths, 0)
+
+    def render_warped_path(self, H, W, K, chunk, render_poses, images_idx, render_kwargs, render_factor=0):
+        """models/lushnerf.py:898-947: for pose i, a pose of training view images_idx[i], the num_motion + 1 sharp images along
+        the camera motion the blur kernel holds for that view (sub-frame 0: the pose itself) and the warped rays of the centre
+        pixel, the trajectory -> (rgbs [V,M+1,H,W,3], depths [V,M+1,H,W,1], rays_save [V,M+1,3,2]).  Colours are linear as in
+        the reference; the caller applies tonemapping() (run_lushnerf.py:461-475 scales and writes them).
+
+        The reference's own body cannot run: :925 unpacks the two values of Rigid_Blurring_Kernel.forward into three names.
+        This is what it computes once that line has its two values; `forward` does not dispatch here, as in the reference.
+
+        One kernel per pose (ops.warp_image) writes the ray batch with its rows SUB-FRAME-MAJOR, so the march's outputs are the
+        [M+1,H,W] images as they stand: no ray table, no warped rays and no permuting copy exist.  A ray's result does not
+        depend on its row, but its random draws do: with perturb > 0 or raw_noise_std > 0 a ray takes another draw than in
+        the reference's ray-major order.  Parity holds for render_kwargs_test (perturb=False, raw_noise_std=0), the only way
+        the reference calls it.  `c2w_staticcam`, `use_awp` and use_viewdirs=False are refused as everywhere."""
+        if getattr(self, "mlp_rbk", None) is None:
+            raise ValueError("render_warped_path renders the sub-frames of the blur kernel: this model has no blur-kernel network "
+                             "(blur_kernel_net=None, or a blur_model_type other than 'dpnerf')")
+        if render_factor != 0:
+            H, W = H // render_factor, W // render_factor
+        kw = dict(render_kwargs)
+        kw.pop('save_warped_ray_img', None)      # (a key of render_kwargs_test, run_lushnerf.py:410, that forward() pops)
+        ndc, near, far = kw.get('ndc', True), kw.get('near', 0.), kw.get('far', 1.)
+        if not kw.get('use_viewdirs', False):
+            raise NotImplementedError("use_viewdirs=False is not built (every config sets it)")
+        self._refuse_unbuilt(kw.get('c2w_staticcam'), kw.get('use_awp', False))
+        if len(images_idx) != len(render_poses):
+            raise ValueError(f"render_warped_path: {len(render_poses)} poses but {len(images_idx)} image indices")
+        M1 = self.mlp_rbk.num_motion + 1
+        rgbs, depths, rays_save, acts = [], [], [], None
+        with torch.no_grad():
+            for i, c2w in enumerate(render_poses):
+                idx = torch.as_tensor(images_idx[i])
+                batch, centre, acts = self.mlp_rbk.warp_image(c2w, idx, H, W, K, ndc, near, far, acts=acts, hooks=self.hooks)
+                rgb, depth, acc, extras = self._render_train_scene_packed(batch, chunk, keep=('rgb_map', 'depth_map', 'acc_map'), **kw)
+                rgbs.append(rgb.view(M1, H, W, 3)); depths.append(depth.view(M1, H, W, 1)); rays_save.append(centre)
+        return torch.stack(rgbs, 0), torch.stack(depths, 0), torch.stack(rays_save, 0)
 
     def Render_Aligned_Pixel(self, H, W, K, chunk, render_poses, images_idx, render_kwargs, render_factor=0,
                              align_matrix=None, align_mask=None, anchor_pose=None, samples=None):

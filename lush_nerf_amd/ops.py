@@ -925,6 +925,45 @@ class RbkWarpNdc(torch.autograd.Function):
         return (drays, None, None, None, None, None, None, None, None, None, None, None, *grads)
 
 
+def rbk_acts(num_motion, window, *params):
+    """The blur-kernel MLP for every view (lush_rbk_mlp_fwd): -> acts [num_img, RBK_ACT], what the warp kernels read."""
+    tensors = [_f32(p) for p in params]
+    acts = torch.empty(tensors[0].shape[0], RBK_ACT, dtype=torch.float32, device=tensors[0].device)
+    st = lib.rbk_struct(tensors)
+    lib.call("lush_rbk_mlp_fwd", C.byref(st), acts.shape[0], int(num_motion), float(window), lib.ptr(acts), _stream())
+    return acts
+
+
+def warp_image(c2w, image_idx, H, W, K, ndc, near, far, num_motion, window, hooks: Optional[Hooks], *rbk_params, acts=None):
+    """The ray batch of NeRFAll.render_warped_path (models/lushnerf.py:898-947) for one pose in one kernel (lush_warp_image_fwd,
+    include/lush_subframe.h): get_rays of every pixel (:917), the blur kernel's warp of view `image_idx` (:921-925) and the head of
+    render_train_scene (:929 -> :772-795).  c2w [3(+),4], image_idx a 0-dim or 1-element integer tensor (it stays on the device:
+    the kernel reads it) -> (ray batch [(M+1)*H*W, 11] with rows SUB-FRAME-MAJOR: row m*H*W + y*W + x, centre_rays [M+1,3,2] = the
+    warped rays of pixel (H//2, W//2) that :926 keeps, acts).  `acts` [num_img, RBK_ACT] is the blur-kernel MLP's output for every
+    view (rbk_acts); None computes it here, a caller with several poses passes the returned one back in.  `hooks` is taken as by
+    every op; none of its switches applies to this kernel.
+    Forward only: this is NOT an autograd Function and no gradient reaches c2w or the blur-kernel parameters (the reference
+    calls it under render_kwargs_test for pictures; training goes through RbkWarpNdc)."""
+    c2w = _f32(c2w[:3, :4].detach())
+    dev = c2w.device
+    H, W, M = int(H), int(W), int(num_motion)
+    if image_idx.numel() != 1 or image_idx.is_floating_point() or image_idx.is_complex():
+        raise ValueError("ops.warp_image: image_idx is ONE integer index (a 0-dim or 1-element integer tensor)")
+    idx = image_idx.detach().reshape(1).to(device=dev, dtype=torch.int64)
+    if acts is None:
+        acts = rbk_acts(M, window, *(p.detach() for p in rbk_params))
+    elif acts.dim() != 2 or acts.shape[1] != RBK_ACT or acts.dtype != torch.float32 or not acts.is_cuda or not acts.is_contiguous():
+        raise ValueError(f"ops.warp_image: acts must be a contiguous fp32 device tensor [num_img, {RBK_ACT}] (ops.rbk_acts)")
+    if not (0 < H * W * (M + 1) < 2 ** 31) or H <= 0:
+        raise ValueError(f"ops.warp_image: {H} x {W} x {M + 1} sub-frames is empty or beyond the 2^31 - 1 rays of one march")
+    cx, cy = _ndc_consts(H, W, float(K[0][0]))
+    batch = torch.empty(H * W * (M + 1), 11, dtype=torch.float32, device=dev)
+    centre = torch.empty(M + 1, 3, 2, dtype=torch.float32, device=dev)
+    lib.call("lush_warp_image_fwd", lib.ptr(c2w), H, W, float(K[0][0]), float(K[1][1]), float(K[0][2]), float(K[1][2]), lib.ptr(idx),
+             acts.shape[0], M, lib.ptr(acts), int(bool(ndc)), cx, cy, float(near), float(far), lib.ptr(batch), lib.ptr(centre), _stream())
+    return batch, centre, acts
+
+
 class BlurMix(torch.autograd.Function):
     """The tail of NeRFAll.forward's training branch in one kernel per direction (SURVEY.md section 7.2 `blur_mix_tonemap`;
     models/lushnerf.py:644-654): rbk_weighted_sum of the fine and coarse colours (:100-116), rgb_noise = 0.1 sigmoid(noise_raw),
