@@ -4,6 +4,7 @@
 #include <cstring>
 #include <vector>
 #include "../../include/lush_march.h"
+#include "../../include/lush_live_fwd.h"
 
 using namespace lush;
 
@@ -468,6 +469,7 @@ namespace {
 struct FwdRequest {
     int net, planes, stash_planes; const float *rays, *z; int R, S; const void* packed; float* raw; void* stash; int variant;
     lush_stream_t stream; const int *live_idx, *live_cnt;
+    bool trunk_only;      // lush_mlp_fwd_trunk: layers 0 .. 7 and the alpha head, raw = (0, 0, 0, sigma)
 };
 int mlp_fwd(const FwdRequest& q) {
     const int net = q.net, planes = q.planes;
@@ -507,6 +509,13 @@ int mlp_fwd(const FwdRequest& q) {
     if (q.live_idx || q.live_cnt) {
         if (!q.live_idx || !q.live_cnt) return set_error("lush_mlp_fwd_live: the list and its count come together");
         if (net != 0 || !chain || (q.variant & LIVE_OLDER_VARIANTS) || stash_planes < 1) return set_error("lush_mlp_fwd_live: the 8x256 net's one- or two-plane kernels with the stash, no older-kernel variant");
+        // (only the 64-points-per-wave kernel writes the rows of a live-point launch)
+        if (q.raw && (planes != PLANES_F16 || stash_planes != 1)) return set_error("lush_mlp_fwd_live_raw: one fp16 plane with its stash");
+    }
+    if (q.trunk_only) {
+        if (net != 0 || planes != PLANES_F16 || stash_planes != 0 || (q.variant & (LUSH_VARIANT_FWD_HALF | LUSH_VARIANT_FWD_512)) || q.live_idx || !q.raw)
+            return set_error("lush_mlp_fwd_trunk: the 8x256 net's one-fp16-plane 64-points-per-wave kernel over all the points, no stash, no older-kernel variant");
+        a.trunk_only = 1;
     }
     if (chain) return launch_mlp_chain_fwd(net, planes, a, q.variant, (hipStream_t)q.stream);
     const int grid = a.n_tiles < 1024 ? a.n_tiles : 1024;
@@ -759,6 +768,16 @@ int lush_mlp_fwd_live(int net, int planes, int stash_planes, const float* rays, 
                       const lush_mlp_params*, void* stash, const int* live_idx, const int* live_cnt, int variant, lush_stream_t stream) {
     if (!live_idx || !live_cnt) return set_error("lush_mlp_fwd_live: live_idx and live_cnt are required");
     return mlp_fwd({net, planes, stash_planes, rays, z, R, S, packed, nullptr, stash, variant, stream, live_idx, live_cnt});
+}
+
+int lush_mlp_fwd_live_raw(int net, int planes, int stash_planes, const float* rays, const float* z, int R, int S, const void* packed,
+                          void* stash, const int* live_idx, const int* live_cnt, float* raw, int variant, lush_stream_t stream) {
+    if (!live_idx || !live_cnt) return set_error("lush_mlp_fwd_live_raw: live_idx and live_cnt are required");
+    return mlp_fwd({net, planes, stash_planes, rays, z, R, S, packed, raw, stash, variant, stream, live_idx, live_cnt});
+}
+int lush_mlp_fwd_trunk(int net, int planes, const float* rays, const float* z, int R, int S, const void* packed, float* raw,
+                       void* workspace, int variant, lush_stream_t stream) {
+    return mlp_fwd({net, planes, 0, rays, z, R, S, packed, raw, workspace, variant, stream, nullptr, nullptr, true});
 }
 
 int lush_mlp_bwd(int net, int planes_f, int planes_b, const float* rays, const float* z, int R, int S,

@@ -17,6 +17,19 @@ struct CompIn {
     int white_bkgd;
 };
 
+// The one statement of which samples before the last pass density on: the clamp of raw2outputs (pre = raw sigma + noise) and
+// near_mask.  A sample that fails it has density 0, alpha 0, weight 0 and an exactly zero d_raw row.  comp_load and the forward's
+// live list (live_fwd_pred, lush_march.hip) both ask here: a point the list missed would keep colour 0 at a non-zero weight.
+__device__ __forceinline__ bool comp_gate(float pre, float znext, float near_mask) {
+    return pre > 0.f && !(near_mask >= 0.f && !(znext > near_mask));
+}
+// pre-activation of sample j < S-1 of a ray as the compositing sees it
+__device__ __forceinline__ float comp_pre(float sigma, const float* noise, float noise_std, long long ray, int S, int j) {
+    float pre = sigma;
+    if (noise != nullptr && noise_std > 0.f) pre += noise[ray * (S - 1) + j] * noise_std;
+    return pre;
+}
+
 template <int SPL>
 __device__ __forceinline__ void comp_load(const CompIn& c, int ray, int lane, float (&alpha)[SPL], float (&dist)[SPL],
                                           float (&dens)[SPL], float (&gate)[SPL], float (&zz)[SPL],
@@ -41,14 +54,10 @@ __device__ __forceinline__ void comp_load(const CompIn& c, int ray, int lane, fl
             if (j < c.S - 1) {
                 const float znext = c.z[p + 1];
                 dist[e] = (znext - zz[e]) * norm;
-                float pre = rw.w;
-                if (c.noise != nullptr && c.noise_std > 0.f)
-                    pre += c.noise[(long long)ray * (c.S - 1) + j] * c.noise_std;
-                float g = pre > 0.f ? 1.f : 0.f;
-                float d = fmaxf(pre, 0.f);
-                if (c.near_mask >= 0.f && !(znext > c.near_mask)) { d = 0.f; g = 0.f; }
-                dens[e] = d; gate[e] = g;
-                alpha[e] = 1.f - expf(-d * dist[e]);
+                const float pre = comp_pre(rw.w, c.noise, c.noise_std, ray, c.S, j);
+                const bool open = comp_gate(pre, znext, c.near_mask);
+                dens[e] = open ? fmaxf(pre, 0.f) : 0.f; gate[e] = open ? 1.f : 0.f;
+                alpha[e] = 1.f - expf(-dens[e] * dist[e]);
             } else {
                 alpha[e] = 1.f;   // last sample: models/lushnerf.py:338
             }

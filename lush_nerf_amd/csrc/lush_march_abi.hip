@@ -7,6 +7,7 @@
 #include "lush_common.h"
 #include "lush_host.h"
 #include "../../include/lush_march.h"
+#include "../../include/lush_live_fwd.h"
 
 using namespace lush;
 
@@ -36,6 +37,13 @@ struct Layout {
 inline bool live_mode(const lush_march_cfg* c) {
     return c->planes_bwd != 0 && !(c->variant & LUSH_VARIANT_DENSE_BWD) &&
            mlp_live_kernels(0, c->planes_fwd, c->planes_bwd, c->variant & LUSH_VARIANT_KERNEL_BITS & ~LUSH_VARIANT_DENSE_BWD);
+}
+
+// The final pass's forward runs trunk-only over all the points and in full, with the stash, on the points of non-zero alpha
+// (include/lush_live_fwd.h): the live-point march whose forward is the product's 64-points-per-wave fp16 kernel.  Asked by
+// lush_march_fwd, lush_march_bwd and, through lush_march_trunk_form, by the Python side -- nobody restates it.
+inline bool trunk_form(const lush_march_cfg* c) {
+    return live_mode(c) && c->planes_fwd == PLANES_F16 && !(c->variant & (LUSH_VARIANT_FWD_HALF | LUSH_VARIANT_FWD_512 | LUSH_VARIANT_PE_ROWS));
 }
 
 bool layout(const lush_march_cfg* c, Layout& L) {
@@ -115,6 +123,11 @@ int lush_march_view(const lush_march_cfg* cfg, int which, size_t* offset, size_t
     }
 }
 
+int lush_march_trunk_form(const lush_march_cfg* cfg) {
+    Layout L;
+    return layout(cfg, L) && trunk_form(cfg) ? 1 : 0;
+}
+
 int lush_march_fwd(const lush_march_cfg* cfg, const float* rays, const lush_mlp_params* coarse, const lush_mlp_params* fine,
                    const lush_march_draws* draws, const lush_march_out* out, void* workspace, int* flags, lush_stream_t st) {
     Layout L;
@@ -133,6 +146,21 @@ int lush_march_fwd(const lush_march_cfg* cfg, const float* rays, const lush_mlp_
     const float* noise_c = draws && cfg->raw_noise_std > 0.f ? draws->noise_c : nullptr;
     const float* u = draws && cfg->perturb > 0.f ? draws->u : nullptr;
     const float* noise_f = draws && cfg->raw_noise_std > 0.f ? draws->noise_f : nullptr;
+    // the MLP forward of a pass.  The final pass in the trunk form: sigma of every point, the list of the points whose alpha is
+    // not zero (into the backward's list regions; its length beside the LIVE_COUNTS words), all of the net WITH the stash on the
+    // list, which writes their rows.  A row the list leaves out keeps rgb = 0: finite, and multiplied by a weight of exactly 0.
+    const bool trunk = trunk_form(cfg);
+    auto mlp = [&](bool final_pass, const float* z, int Sp, const void* pk, const lush_mlp_params* prm, size_t rawoff, size_t stashoff, const float* noise) -> int {
+        float* raw = (float*)(w + rawoff);
+        if (!(trunk && final_pass)) return lush_mlp_fwd(0, pf, sc, rays, z, R, Sp, pk, prm, raw, w + stashoff, var, st);
+        int* lidx = (int*)(w + L.live_idx);
+        int* list_cnt = (int*)(w + L.live_cnt) + LUSH_LIVE_LIST_COUNT_WORD;
+        int r = lush_mlp_fwd_trunk(0, pf, rays, z, R, Sp, pk, raw, w + stashoff, var, st);
+        if (r) return r;
+        r = lush_live_list(raw, z, noise, cfg->raw_noise_std, cfg->near_mask, R, Sp, lidx, (int*)(w + L.ray_start), list_cnt, w + L.live_aux, st);
+        if (r) return r;
+        return lush_mlp_fwd_live_raw(0, pf, stash_code(pf, cfg->planes_bwd), rays, z, R, Sp, pk, w + stashoff, lidx, list_cnt, raw, var, st);
+    };
     float* zc = (float*)(w + L.zc);
     int rc = lush_zgrid(rays, R, S, cfg->lindisp, t_rand, zc, st);
     if (rc) return rc;
@@ -143,7 +171,7 @@ int lush_march_fwd(const lush_march_cfg* cfg, const float* rays, const lush_mlp_
         if (rc) return rc;
         pkc = w + L.pkc;
     }
-    rc = lush_mlp_fwd(0, pf, sc, rays, zc, R, S, pkc, coarse, (float*)(w + L.rawc), w + L.stashc, var, st);
+    rc = mlp(!two, zc, S, pkc, coarse, L.rawc, L.stashc, noise_c);
     if (rc) return rc;
     // the coarse pass's results are rgb0 .. when a fine pass follows, else the final ones
     rc = lush_composite_fwd((const float*)(w + L.rawc), zc, rays, R, S, noise_c, cfg->raw_noise_std, cfg->near_mask, cfg->white_bkgd,
@@ -159,7 +187,7 @@ int lush_march_fwd(const lush_march_cfg* cfg, const float* rays, const lush_mlp_
         if (rc) return rc;
         pkf = w + L.pkf;
     }
-    rc = lush_mlp_fwd(0, pf, sc, rays, zf, R, Sf, pkf, pfine, (float*)(w + L.rawf), w + L.stashf, var, st);
+    rc = mlp(true, zf, Sf, pkf, pfine, L.rawf, L.stashf, noise_f);
     if (rc) return rc;
     return lush_composite_fwd((const float*)(w + L.rawf), zf, rays, R, Sf, noise_f, cfg->raw_noise_std, cfg->near_mask, cfg->white_bkgd,
                               out->rgb, out->depth, out->acc, (float*)(w + L.wf), out->density, flags, 0, st);
@@ -180,6 +208,10 @@ int lush_march_bwd(const lush_march_cfg* cfg, const float* rays, const lush_mlp_
     const int pf = cfg->planes_fwd, pb = cfg->planes_bwd, sc = stash_code(pf, pb), var = cfg->variant & LUSH_VARIANT_KERNEL_BITS;
     const float* noise_c = draws && cfg->raw_noise_std > 0.f ? draws->noise_c : nullptr;
     const float* noise_f = draws && cfg->raw_noise_std > 0.f ? draws->noise_f : nullptr;
+    // The caller vouches that the workspace is as the lush_march_fwd of this configuration left it: the final pass works on the
+    // forward's list and stash (include/lush_live_fwd.h).  Read here, before `var` loses what is no kernel bit; without the bit
+    // every pass lists its live points and re-runs the forward on them, which is correct after any forward.
+    const bool kept = (cfg->variant & LUSH_MARCH_FWD_LIST_KEPT) && trunk_form(cfg);
     // One pass = compositing backward, (re-pack), gradient chain, d(point) -> d(ray), weight gradients; the fine pass first,
     // then the coarse one (which does not depend on it: z_samples are detached, models/lushnerf.py:546), all on the caller's
     // stream out of one backward scratch.  (Round 3 ran the fine pass's weight gradients on a second stream beside the coarse
@@ -191,7 +223,7 @@ int lush_march_bwd(const lush_march_cfg* cfg, const float* rays, const lush_mlp_
     // fragments of the backward's plane code: the caller's (cfg->packed_*), else the forward's copy in the workspace when the
     // codes agree, else packed here
     auto chain = [&](const lush_mlp_params* prm, size_t zoff, size_t rawoff, size_t stashoff, const void* pk_ready, size_t pkboff, bool repack,
-                     int Sp, const float* noise, const float* g_rgb, const float* g_depth, const float* g_acc, const void* pk_fwd, int slot) -> int {
+                     int Sp, const float* noise, const float* g_rgb, const float* g_depth, const float* g_acc, const void* pk_fwd, int slot, bool from_fwd) -> int {
         const float* z = (const float*)(w + zoff);
         // the compositing backward also leaves the per-workgroup maxima of |d_raw| (in the d(point) array, which the chain only
         // writes afterwards) for the fp16 chain's loss scale, zeroes the weight-gradient scratch and, in the march's first pass,
@@ -222,12 +254,21 @@ int lush_march_bwd(const lush_march_cfg* cfg, const float* rays, const lush_mlp_
             int* lidx = (int*)(w + L.live_idx);
             int* lcnt = (int*)(w + L.live_cnt) + 2 * slot;      // {live points, points} of the fine (slot 0) / coarse (slot 1) pass: LUSH_VIEW_LIVE_COUNTS
             float* draw_c = (float*)(w + L.draw_c);
-            rc = lush_live_compact(x.draw, R, Sp, lidx, draw_c, (int*)(w + L.ray_start), lcnt, w + L.live_aux, st);
-            if (rc) return rc;
-            const void* pkf = pk_fwd;            // forward fragments: the caller's buffer or the forward call's copy in the workspace
-            rc = lush_mlp_fwd_live(0, pf, sc, rays, z, R, Sp, pkf, prm, w + stashoff, lidx, lcnt, var, st);
-            if (rc) return rc;
-            rc = mlp_bwd_chain_prepared(0, sc, pb, rays, z, R, Sp, pk, prm, draw_c, w + stashoff, x.dstash, x.dpts, var, (hipStream_t)st, lidx, lcnt);
+            const int* len = lcnt;               // the length of the list the launches below run on
+            if (from_fwd) {
+                // the forward's list, per-ray ranges and stash stand: d_raw rows in list order (a listed point may have a zero row:
+                // it adds exact zeros), and the count of the non-zero ones for LIVE_COUNTS
+                len = (const int*)(w + L.live_cnt) + LUSH_LIVE_LIST_COUNT_WORD;
+                rc = lush_live_gather(x.draw, R, Sp, lidx, len, draw_c, lcnt, st);
+                if (rc) return rc;
+            } else {
+                rc = lush_live_compact(x.draw, R, Sp, lidx, draw_c, (int*)(w + L.ray_start), lcnt, w + L.live_aux, st);
+                if (rc) return rc;
+                const void* pkf = pk_fwd;            // forward fragments: the caller's buffer or the forward call's copy in the workspace
+                rc = lush_mlp_fwd_live(0, pf, sc, rays, z, R, Sp, pkf, prm, w + stashoff, lidx, lcnt, var, st);
+                if (rc) return rc;
+            }
+            rc = mlp_bwd_chain_prepared(0, sc, pb, rays, z, R, Sp, pk, prm, draw_c, w + stashoff, x.dstash, x.dpts, var, (hipStream_t)st, lidx, len);
             if (rc) return rc;
             return lush_ray_grad_reduce_live(x.dpts, z, lidx, (const int*)(w + L.ray_start), R, drays, st);
         }
@@ -235,8 +276,9 @@ int lush_march_bwd(const lush_march_cfg* cfg, const float* rays, const lush_mlp_
         if (rc) return rc;
         return lush_ray_grad_reduce(x.dpts, z, R, Sp, drays, st);
     };
-    auto weights = [&](const lush_mlp_params* prm, const lush_mlp_grads* gr, size_t stashoff, int Sp, int slot) -> int {
-        if (L.live) return mlp_bwd_weights_prepared(0, sc, pb, R, Sp, prm, (const float*)(w + L.draw_c), w + stashoff, x.dstash, gr, var, (hipStream_t)st, (const int*)(w + L.live_cnt) + 2 * slot);
+    auto weights = [&](const lush_mlp_params* prm, const lush_mlp_grads* gr, size_t stashoff, int Sp, int slot, bool from_fwd) -> int {
+        if (L.live) return mlp_bwd_weights_prepared(0, sc, pb, R, Sp, prm, (const float*)(w + L.draw_c), w + stashoff, x.dstash, gr, var, (hipStream_t)st,
+                                                    (const int*)(w + L.live_cnt) + (from_fwd ? LUSH_LIVE_LIST_COUNT_WORD : 2 * slot));
         return mlp_bwd_weights_prepared(0, sc, pb, R, Sp, prm, x.draw, w + stashoff, x.dstash, gr, var, (hipStream_t)st);
     };
     const bool any_main = g->rgb || g->depth || g->acc;
@@ -250,17 +292,17 @@ int lush_march_bwd(const lush_march_cfg* cfg, const float* rays, const lush_mlp_
     const void* ready_f = cfg->same_net ? ready_c : (pb == pf ? cfg->packed_fine : cfg->packed_bwd_fine);
     if (two && any_main) {
         rc = chain(pfine, L.zf, L.rawf, L.stashf, ready_f, L.pkbf, pb != pf, Sf, noise_f, g->rgb, g->depth, g->acc,
-                   cfg->same_net ? (cfg->packed_coarse ? cfg->packed_coarse : (const void*)(w + L.pkc)) : (cfg->packed_fine ? cfg->packed_fine : (const void*)(w + L.pkf)), 0);
+                   cfg->same_net ? (cfg->packed_coarse ? cfg->packed_coarse : (const void*)(w + L.pkc)) : (cfg->packed_fine ? cfg->packed_fine : (const void*)(w + L.pkf)), 0, kept);
         if (rc) return rc;
         packed_b_c = cfg->same_net && pb != pf;     // the shared net's backward fragments are packed now
-        rc = weights(pfine, gfine, L.stashf, Sf, 0);
+        rc = weights(pfine, gfine, L.stashf, Sf, 0, kept);
         if (rc) return rc;
     }
     if (any_c) {
         rc = chain(coarse, L.zc, L.rawc, L.stashc, ready_c, L.pkbc, pb != pf && !packed_b_c, S, noise_c, two ? g->rgb0 : g->rgb,
-                   two ? g->depth0 : g->depth, two ? g->acc0 : g->acc, cfg->packed_coarse ? cfg->packed_coarse : (const void*)(w + L.pkc), two ? 1 : 0);
+                   two ? g->depth0 : g->depth, two ? g->acc0 : g->acc, cfg->packed_coarse ? cfg->packed_coarse : (const void*)(w + L.pkc), two ? 1 : 0, kept && !two);
         if (rc) return rc;
-        rc = weights(coarse, g_coarse, L.stashc, S, two ? 1 : 0);
+        rc = weights(coarse, g_coarse, L.stashc, S, two ? 1 : 0, kept && !two);
     }
     return rc;
 }

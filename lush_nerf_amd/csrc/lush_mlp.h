@@ -182,6 +182,9 @@ struct MlpFwdArgs {
     // `raw` is not written (the caller has it from the pass over all points).  Both null: a launch over all the points.
     const int* live_idx;
     const int* live_cnt;
+    // The 64-points-per-wave kernel only: a live-point launch with `raw` non-null writes its i-th row to raw[live_idx[i]];
+    // trunk_only (a launch over all the points, no stash): layers 0 .. NL-1 and the alpha head, raw = (0, 0, 0, sigma).
+    int trunk_only;
 };
 
 struct MlpBwdArgs {

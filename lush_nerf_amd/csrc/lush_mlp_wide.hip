@@ -33,12 +33,22 @@ namespace lush {
 // block instead of one per (column block, chunk): the XOR-swizzled addresses were hoisted out of the tile loop and spilled).
 constexpr int WD_PE_PITCH = PE_ROW * 2 + 16;
 constexpr int WD_PE_PLANE = WD_MT * WD_PE_PITCH;
+constexpr int WD_PE_LIVE = (PE_X + PE_D) * 2;     // first byte of a row behind the encoded values
+static_assert(WD_PE_LIVE + 4 <= WD_PE_PITCH, "a row has room for the point's grid index");
 constexpr int WD_SB = 2;                // stash rows in flight between their LDS read-back and their store
 enum { WB_NONE = 0, WB_REG = 1, WB_PEX = 2, WB_PED = 3 };     // B operand of a position
 enum { WC_NONE = 0, WC_ACT = 1, WC_ALPHA = 2 };               // what happens to the pending accumulator set
 
 constexpr int WD_WRAP = NetNerf::fwd4_len / 8;      // stream positions per tile
 static_assert(NetNerf::fwd4_len % 8 == 0, "the quarter-row stream is whole positions");
+// The trunk-only instantiation (TRUNK: layers 0 .. 7 and the alpha head, raw = (0, 0, 0, sigma)) reads the same stream and
+// leaves out what lies between layer 7 and the alpha head (the feature layer) and behind the alpha head (views, rgb):
+// positions 0 .. WD_TR_JUMP-1, then WD_TR_ALPHA and WD_TR_ALPHA + 1, then position 0 of the next tile.
+constexpr int WD_TR_JUMP = 4 + 7 * 16 + 4;          // layer 0, layers 1..7, the skip layer's four gamma(x) positions
+constexpr int WD_TR_ALPHA = WD_TR_JUMP + 16;        // behind the feature layer's 16 positions
+constexpr int WD_TR_WRAP = WD_TR_JUMP + 2;          // positions per tile of that instantiation
+static_assert(WD_TR_ALPHA + 2 + 10 + 1 == WD_WRAP && WD_TR_WRAP == 122, "trunk | feature | alpha | views | rgb");
+static_assert(WD_S < WD_TR_JUMP, "the prologue's positions are plain trunk positions");
 
 LUSH_CLOCK_DECL(lush_clock_wide_fwd)
 
@@ -133,7 +143,7 @@ struct WdConv {
 // bias re-loads, in dependency order -- are poured into the gaps up to a cap of issue slots per gap (raised only if the
 // pass's deadline D could not be met otherwise).
 
-template <int NRQ, int NPOS, int BMAIN, int KB0, int PRE, int CK, int NRQP, int CKB0, bool MASK, int NRQN, int D, int PQ, bool STASH, int LD>
+template <int NRQ, int NPOS, int BMAIN, int KB0, int PRE, int CK, int NRQP, int CKB0, bool MASK, int NRQN, int D, int PQ, bool STASH, int LD, bool TRUNK = false>
 struct WdPass {
     static constexpr int KBPP = 8 / NRQ;
     static constexpr int NG = NPOS * 16;
@@ -254,7 +264,12 @@ struct WdPass {
             r.dma_dst = cx.dma_base + cx.slot_off;              // refill the slot this position frees ...
             r.dma_off = cx.fetch_off;                           // ... with stream position +S
         } else if constexpr (M == 5) {
-            cx.fetch_off = cx.fetch_off + WD_SLOT == (unsigned)WD_WRAP * WD_SLOT ? 0u : cx.fetch_off + WD_SLOT;
+            if constexpr (TRUNK) {      // over the feature layer's positions, and back to 0 behind the alpha head's second one
+                const unsigned f = cx.fetch_off + WD_SLOT == (unsigned)WD_TR_JUMP * WD_SLOT ? (unsigned)WD_TR_ALPHA * WD_SLOT : cx.fetch_off + WD_SLOT;
+                cx.fetch_off = f == (unsigned)(WD_TR_ALPHA + 2) * WD_SLOT ? 0u : f;
+            } else {
+                cx.fetch_off = cx.fetch_off + WD_SLOT == (unsigned)WD_WRAP * WD_SLOT ? 0u : cx.fetch_off + WD_SLOT;
+            }
             cx.slot_off = cx.slot_off + WD_SLOT == (unsigned)WD_S * WD_SLOT ? 0u : cx.slot_off + WD_SLOT;
         } else if constexpr (M == 8) {
             wd_dma_pair(cx.gbase + r.dma_off, cx.gbase + r.dma_off + 4096u, cx.voff, r.dma_dst, r.dma_dst + 4096u);
@@ -430,6 +445,9 @@ __device__ __noinline__ void wd_pe_tile(char* peimg, const float* rays, const fl
         for (int k = 0; k < L_D; ++k) sincos_rev(hd, ld, k, &v[PE_X + 3 + 6 * k + i], &v[PE_X + 3 + 6 * k + 3 + i]);
     }
     char* row = peimg + tid * WD_PE_PITCH;
+    // a live-point launch that writes `raw`: the point's grid index waits in the row's padding (bytes the K loops never read)
+    // for the tile's raw store, which then needs no global load of its own
+    if (live) *reinterpret_cast<int*>(row + WD_PE_LIVE) = gpt < P ? live[gpt] : 0;
 #pragma unroll
     for (int c = 0; c < (PE_X + PE_D) / 8; ++c) {
         u32x4 w;
@@ -463,9 +481,11 @@ __device__ __forceinline__ void wd_bias(f32x16 (&acc)[2][2], const float* b, int
         }
 }
 
-template <class N, int SPK>
+template <class N, int SPK, bool TRUNK = false>
 __global__ __launch_bounds__(WD_NT) void mlp_wide_fwd_kernel(const MlpFwdArgs A) {
     static_assert(N::HW == 256 && N::NL == 8 && N::HV == 128, "the wide kernel is built for the 8x256 net");
+    static_assert(!TRUNK || SPK == 0, "the trunk-only pass over all points keeps no stash");
+    static_assert(!TRUNK || N::SKIP < N::NL - 1,"layer 7 of the trunk-only pass is a plain layer");
     constexpr int HW = N::HW, HV = N::HV, NL = N::NL, NRB = N::NRB;
     constexpr int NBIAS = N::f32_w_rgb;
     constexpr bool MASK = SPK > 0;
@@ -527,6 +547,8 @@ __global__ __launch_bounds__(WD_NT) void mlp_wide_fwd_kernel(const MlpFwdArgs A)
         // Later tiles: that DMA left S positions ago, in the views layer's second quarter; younger are the DMAs of S-1
         // positions and AT LEAST the 16 stash stores of the views hidden + the raw store (an undercount is safe) -- a full
         // drain here would wait for every stash store of the tile to reach memory (microseconds, 40 times per launch).
+        // (TRUNK: that DMA left in layer NL-1's last quarter; younger are the DMAs of S-1 positions and the raw store, which every
+        // wave issues -- a tile that has a successor is a full tile: the count of SPK == 0 holds)
         if (tile == (int)blockIdx.x) wd_wait_vm<2 * (WD_S - 1)>();
         else wd_wait_vm<2 * (WD_S - 1) + (SPK > 0 ? 17 : 1)>();
         lds_barrier();
@@ -563,13 +585,13 @@ __global__ __launch_bounds__(WD_NT) void mlp_wide_fwd_kernel(const MlpFwdArgs A)
 
         // ---- layer 0: gamma(x) from the PE image, four quarter passes of one position ----
         rt.clamp = 0u;
-        WdPass<2, 1, WB_PEX, 0, WB_NONE, WC_NONE, 2, 0, MASK, 2, 16, 0, false, HW>::run(cx, accA, accB, B0, B0, a0, peimg, row0, rt, alpha);
+        WdPass<2, 1, WB_PEX, 0, WB_NONE, WC_NONE, 2, 0, MASK, 2, 16, 0, false, HW, TRUNK>::run(cx, accA, accB, B0, B0, a0, peimg, row0, rt, alpha);
         mset(0, 0, false); rt.nextbias = btr + 128;
-        WdPass<2, 1, WB_PEX, 0, WB_NONE, WC_ACT, 2, 0, MASK, 2, 16, 0, false, HW>::run(cx, accB, accA, B0, B0, a0, peimg, row0, rt, alpha);
+        WdPass<2, 1, WB_PEX, 0, WB_NONE, WC_ACT, 2, 0, MASK, 2, 16, 0, false, HW, TRUNK>::run(cx, accB, accA, B0, B0, a0, peimg, row0, rt, alpha);
         mset(0, 2, false); rt.nextbias = btr + 192;
-        WdPass<2, 1, WB_PEX, 0, WB_NONE, WC_ACT, 2, 4, MASK, 2, 16, 0, false, HW>::run(cx, accA, accB, B0, B0, a0, peimg, row0, rt, alpha);
+        WdPass<2, 1, WB_PEX, 0, WB_NONE, WC_ACT, 2, 4, MASK, 2, 16, 0, false, HW, TRUNK>::run(cx, accA, accB, B0, B0, a0, peimg, row0, rt, alpha);
         mset(0, 4, false); rt.nextbias = btr + HW;
-        WdPass<2, 1, WB_PEX, 0, WB_NONE, WC_ACT, 2, 8, MASK, 2, 16, 0, false, HW>::run(cx, accB, accA, B0, B0, a0, peimg, row0, rt, alpha);
+        WdPass<2, 1, WB_PEX, 0, WB_NONE, WC_ACT, 2, 8, MASK, 2, 16, 0, false, HW, TRUNK>::run(cx, accB, accA, B0, B0, a0, peimg, row0, rt, alpha);
 
         // ---- layers 1 .. NL-1 and the feature layer (l = NL: no activation, no decision words), two per iteration so
         // that the B-operand buffers swap roles without copies: odd member B0 -> B1, even member B1 -> B0 ----
@@ -580,30 +602,55 @@ __global__ __launch_bounds__(WD_NT) void mlp_wide_fwd_kernel(const MlpFwdArgs A)
             rt.srows = reinterpret_cast<char*>(A.h0 + (long long)(l - 1) * A.h_stride + wpt * HW);
             // pass 0: set A accumulates rows 0..63; set B (last quarter of the previous layer) -> xin k-blocks 12..15
             rt.clamp = 0u; mset(l - 1, 6, false); rt.nextbias = bl + 64;
-            WdPass<2, 4, WB_REG, 0, WB_PEX, WC_ACT, 2, 12, MASK, 2, 48, 0, (SPK > 0), HW>::run(cx, accA, accB, xin, xin, a0, peimg, row0, rt, alpha);
+            WdPass<2, 4, WB_REG, 0, WB_PEX, WC_ACT, 2, 12, MASK, 2, 48, 0, (SPK > 0), HW, TRUNK>::run(cx, accA, accB, xin, xin, a0, peimg, row0, rt, alpha);
             rt.clamp = feat ? 0x80008000u : 0u;
             mset(l, 0, feat); rt.nextbias = bl + 128;
-            WdPass<2, 4, WB_REG, 0, WB_PEX, WC_ACT, 2, 0, MASK, 2, 60, 1, (SPK > 0), HW>::run(cx, accB, accA, xin, xout, a0, peimg, row0, rt, alpha);
+            WdPass<2, 4, WB_REG, 0, WB_PEX, WC_ACT, 2, 0, MASK, 2, 60, 1, (SPK > 0), HW, TRUNK>::run(cx, accB, accA, xin, xout, a0, peimg, row0, rt, alpha);
             mset(l, 2, feat); rt.nextbias = bl + 192;
-            WdPass<2, 4, WB_REG, 0, WB_PEX, WC_ACT, 2, 4, MASK, 2, 60, 2, (SPK > 0), HW>::run(cx, accA, accB, xin, xout, a0, peimg, row0, rt, alpha);
-            mset(l, 4, feat); rt.nextbias = feat ? biasl + N::f32_b_alpha : bl + HW;
-            WdPass<2, 4, WB_REG, 0, WB_PEX, WC_ACT, 2, 8, MASK, 2, 60, 3, (SPK > 0), HW>::run(cx, accB, accA, xin, xout, a0, peimg, row0, rt, alpha);
+            WdPass<2, 4, WB_REG, 0, WB_PEX, WC_ACT, 2, 4, MASK, 2, 60, 2, (SPK > 0), HW, TRUNK>::run(cx, accA, accB, xin, xout, a0, peimg, row0, rt, alpha);
+            // (TRUNK: the alpha head follows layer NL-1 directly)
+            mset(l, 4, feat); rt.nextbias = (feat || (TRUNK && l == NL - 1)) ? biasl + N::f32_b_alpha : bl + HW;
+            WdPass<2, 4, WB_REG, 0, WB_PEX, WC_ACT, 2, 8, MASK, 2, 60, 3, (SPK > 0), HW, TRUNK>::run(cx, accB, accA, xin, xout, a0, peimg, row0, rt, alpha);
         };
 #pragma unroll 1
-        for (int l2 = 0; l2 < NL / 2; ++l2) {
+        for (int l2 = 0; l2 < (TRUNK ? NL / 2 - 1 : NL / 2); ++l2) {
             layer(1 + 2 * l2, B0, B1);
             layer(2 + 2 * l2, B1, B0);
+        }
+        if constexpr (TRUNK) {
+            // layer NL-1 is the last one (outside the loop: an exit from the middle of the pair made the register allocator spill):
+            // B1 = h_{NL-1} k-blocks 0..11
+            layer(NL - 1, B0, B1);
+            // Set B holds the last quarter of h_{NL-1}, set A the alpha bias.  The full kernel converts that quarter behind the
+            // feature layer's first pass; here nothing is left to hide it behind but the alpha head itself, whose second position
+            // reads it: the units run straight, as the views layer's second quarter does below.  Same conversion, same operand
+            // bits, and the alpha head's MFMAs in the same order: sigma is the full kernel's bit for bit.
+            {
+                WdConvTmp ct;
+                using CV = WdConv<2, 12, false>;
+                wd_unroll<0, CV::NVU>([&](auto kc) __attribute__((always_inline)) { CV::template unit<decltype(kc)::value>(accB, B1, ct, 0u); });
+            }
+            rt.pre_on = false;
+            WdPass<1, 2, WB_REG, 0, WB_NONE, WC_NONE, 2, 0, false, 2, 16, 0, false, HW, TRUNK>::run(cx, accA, accB, B1, B1, a0, peimg, row0, rt, alpha);
+            if (h == 0) {
+#pragma unroll
+                for (int c = 0; c < 2; ++c) {
+                    const long long gpt = wpt + c * 32 + n;
+                    if (gpt < P) *reinterpret_cast<float4*>(A.raw + gpt * 4) = make_float4(0.f, 0.f, 0.f, accA[c][0][0]);
+                }
+            }
+            continue;
         }
         // now: B1 = h_{NL-1}, B0 = feature k-blocks 0..11; set B holds the feature layer's last quarter, set A the alpha bias
         rt.pre_on = false;
         // ---- alpha head on h_{NL-1} (1 row block, 2 positions); set B -> feature k-blocks 12..15 ----
         rt.clamp = 0x80008000u; mset(0, 0, true); rt.nextbias = biasl + N::f32_b_views;
-        WdPass<1, 2, WB_REG, 0, WB_NONE, WC_ACT, 2, 12, MASK, 2, 32, 0, false, HW>::run(cx, accA, accB, B1, B0, a0, peimg, row0, rt, alpha);
+        WdPass<1, 2, WB_REG, 0, WB_NONE, WC_ACT, 2, 12, MASK, 2, 32, 0, false, HW, TRUNK>::run(cx, accA, accB, B1, B0, a0, peimg, row0, rt, alpha);
         // ---- views layer: relu(Wv [feature ; gamma(d)] + b), two quarter passes ----
         rt.nextbias = biasl + N::f32_b_views + 64;
-        WdPass<2, 4, WB_REG, 0, WB_PED, WC_ALPHA, 1, 0, MASK, 2, 60, 0, false, HW>::run(cx, accB, accA, B0, B0, a0, peimg, row0, rt, alpha);
+        WdPass<2, 4, WB_REG, 0, WB_PED, WC_ALPHA, 1, 0, MASK, 2, 60, 0, false, HW, TRUNK>::run(cx, accB, accA, B0, B0, a0, peimg, row0, rt, alpha);
         rt.clamp = 0u; mset(NL, 0, false); rt.nextbias = biasl + N::f32_b_rgb;
-        WdPass<2, 4, WB_REG, 0, WB_PED, WC_ACT, 2, 0, MASK, 1, 60, 0, false, HW>::run(cx, accA, accB, B0, B1, a0, peimg, row0, rt, alpha);
+        WdPass<2, 4, WB_REG, 0, WB_PED, WC_ACT, 2, 0, MASK, 1, 60, 0, false, HW, TRUNK>::run(cx, accA, accB, B0, B1, a0, peimg, row0, rt, alpha);
         {   // the second views quarter has no MFMAs left to hide behind
             WdConvTmp ct;
             using CV = WdConv<2, 4, MASK>;
@@ -632,18 +679,21 @@ __global__ __launch_bounds__(WD_NT) void mlp_wide_fwd_kernel(const MlpFwdArgs A)
                 }
         }
         // ---- rgb head (1 row block, 1 position) ----
-        WdPass<1, 1, WB_REG, 0, WB_NONE, WC_NONE, 2, 0, MASK, 2, 16, 0, false, HW>::run(cx, accB, accA, B1, B1, a0, peimg, row0, rt, alpha);
+        WdPass<1, 1, WB_REG, 0, WB_NONE, WC_NONE, 2, 0, MASK, 2, 16, 0, false, HW, TRUNK>::run(cx, accB, accA, B1, B1, a0, peimg, row0, rt, alpha);
         if (h == 0) {
 #pragma unroll
             for (int c = 0; c < 2; ++c) {
                 const long long gpt = wpt + c * 32 + n;
-                if (gpt < P && A.live_idx == nullptr) {      // (a live-point launch re-computes points whose raw output the caller has)
+                // (a live-point launch re-computes points whose raw output the caller has, unless it asks for the rows: the trunk-only
+                // pass over all points left their colours out.  Its i-th point is grid point live_idx[i], kept in the PE row.)
+                if (gpt < P && A.raw != nullptr) {
                     float4 o;
                     o.x = accB[c][0][0];
                     o.y = accB[c][0][1];
                     o.z = accB[c][0][2];
                     o.w = alpha[c];
-                    *reinterpret_cast<float4*>(A.raw + gpt * 4) = o;
+                    const long long dst = A.live_idx != nullptr ? (long long)*reinterpret_cast<const int*>(peimg + (row0 + c * 32 + n) * WD_PE_PITCH + WD_PE_LIVE) : gpt;
+                    *reinterpret_cast<float4*>(A.raw + dst * 4) = o;
                 }
             }
         }
@@ -659,9 +709,9 @@ LUSH_CLOCK_EXPORT(lush_debug_clock_fwd, lush_clock_wide_fwd)
 static_assert((NetNerf::f32_w_rgb * 4) % 16 == 0, "the ring behind the bias block stays 16-byte aligned");
 size_t mlp_wide_fwd_lds_bytes() { return (size_t)WD_S * WD_SLOT + (size_t)WD_PE_PLANE + (size_t)NetNerf::f32_w_rgb * 4 + 8 * 4096; }
 
-template <int SPK>
+template <int SPK, bool TRUNK = false>
 static int launch_wide_sp(const MlpFwdArgs& a, hipStream_t s) {
-    auto k = mlp_wide_fwd_kernel<NetNerf, SPK>;
+    auto k = mlp_wide_fwd_kernel<NetNerf, SPK, TRUNK>;
     const size_t lds = mlp_wide_fwd_lds_bytes();
     static KernelOnce once;              // (per instantiation and device: the attribute call costs more than the launch in the small configs)
     int dev = 0, n_cu = 0;
@@ -679,6 +729,10 @@ static int launch_wide_sp(const MlpFwdArgs& a, hipStream_t s) {
 // One fp16 plane, the 8x256 net: a.stash_planes 0 (inference) or 1.
 int launch_mlp_wide_fwd(const MlpFwdArgs& a, hipStream_t s) {
     const int sp = a.write_stash ? a.stash_planes : 0;
+    if (a.trunk_only) {      // layers 0 .. 7 and the alpha head over all the points: raw = (0, 0, 0, sigma)
+        if (sp != 0 || a.live_idx || !a.raw) return set_error("launch_mlp_wide_fwd: the trunk-only pass runs over all the points, without stash");
+        return launch_wide_sp<0, true>(a, s);
+    }
     if (sp == 0) return launch_wide_sp<0>(a, s);
     if (sp == 1) return launch_wide_sp<1>(a, s);
     return set_error("launch_mlp_wide_fwd: one stash plane at most");

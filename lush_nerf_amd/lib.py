@@ -3,7 +3,7 @@
 The shared object is built IN-TREE by ``build()`` (hipcc --offload-arch=gfx950)
 and loaded with ctypes.  There is no fallback: if the library is missing or a
 call fails the product raises.  Signatures, structs and constants are read from include/lush_march.h (abi.py), the one
-later entry point from the second contract header include/lush_subframe.h.
+later entry point from the second contract header include/lush_subframe.h, the trunk form's from the third, include/lush_live_fwd.h.
 """
 from __future__ import annotations
 
@@ -18,7 +18,8 @@ HERE = os.path.dirname(os.path.abspath(__file__))
 CSRC = os.path.join(HERE, "csrc")
 SO_PATH = os.path.join(HERE, "liblush_march.so")      # (developer tools load another build with use_library(path) BEFORE load())
 SOURCES = ["lush_march.hip", "lush_mlp.hip", "lush_mlp_chain.hip", "lush_mlp_wide.hip", "lush_mlp_wide_bwd.hip", "lush_abi.hip", "lush_march_abi.hip", "lush_field.hip"]
-HEADERS = ["lush_common.h", "lush_composite.h", "lush_mlp.h", "lush_mlp_dev.h", "lush_mlp_wide.h", "lush_host.h", os.path.join("..", "..", "include", "lush_subframe.h"),
+HEADERS = ["lush_common.h", "lush_composite.h", "lush_mlp.h", "lush_mlp_dev.h", "lush_mlp_wide.h", "lush_host.h", os.path.join("..", "..", "include", "lush_live_fwd.h"),
+           os.path.join("..", "..", "include", "lush_subframe.h"),
            os.path.join("..", "..", "include", "lush_march.h")]      # (the last one is the contract _abi is read from)
 
 _lib = None
@@ -135,6 +136,13 @@ FAULT_BITS = {n: b for b, n in FAULT_NAMES.items()}
 _abi_subframe = abi.parse(open(os.path.join(CSRC, HEADERS[-2])).read(), "lush_subframe.h")
 _SIGS_SUBFRAME = _abi_subframe.protos
 EXPORTS_SUBFRAME = list(_SIGS_SUBFRAME)
+# The third one, include/lush_live_fwd.h: the training march whose final pass computes colour on live points only -- its pieces,
+# the predicate lush_march_trunk_form and the permission bit MARCH_FWD_LIST_KEPT of lush_march_bwd
+_abi_live_fwd = abi.parse(open(os.path.join(CSRC, HEADERS[-3])).read(), "lush_live_fwd.h")
+_SIGS_LIVE_FWD = _abi_live_fwd.protos
+EXPORTS_LIVE_FWD = list(_SIGS_LIVE_FWD)
+MARCH_FWD_LIST_KEPT = _abi_live_fwd.consts["LUSH_MARCH_FWD_LIST_KEPT"]
+LIVE_LIST_COUNT_WORD = _abi_live_fwd.consts["LUSH_LIVE_LIST_COUNT_WORD"]
 
 
 def fault_names(word: int):
@@ -153,7 +161,7 @@ def load():
         raise RuntimeError(f"{SO_PATH} is missing: run `python -c 'import __graft_entry__ as g; g.build()'` "
                            "(the HIP extension is required; there is no fallback path)")
     lib = C.CDLL(SO_PATH)
-    for name, (args, res) in (*_SIGS.items(), *_SIGS_SUBFRAME.items()):
+    for name, (args, res) in (*_SIGS.items(), *_SIGS_SUBFRAME.items(), *_SIGS_LIVE_FWD.items()):
         fn = getattr(lib, name)
         fn.argtypes = args
         fn.restype = res

@@ -212,10 +212,50 @@ def live_compact(draw: torch.Tensor, R: int, S: int):
     return lidx, draw_c, ray_start, cnt
 
 
+def mlp_forward_trunk(planes: int, packed, rays, z, variant: int = 0, timer: Optional[KernelTimer] = None, group: str = "mlp_fwd_all"):
+    """lush_mlp_fwd_trunk (include/lush_live_fwd.h): layers 0..7 and the alpha head of the NeRF net over all the points,
+    raw [R*S, 4] = (0, 0, 0, sigma) with the full forward's sigma bit for bit."""
+    R, S = z.shape
+    raw = torch.empty(R * S, 4, dtype=torch.float32, device=rays.device)
+    work = torch.empty(max(int(lib.load().lush_mlp_stash_bytes(NET_NERF, planes, 0, R * S)), 4), dtype=torch.uint8, device=rays.device)
+    ev = timer.span(group, R * S) if timer is not None else None
+    if ev:
+        ev[0].record()
+    lib.call("lush_mlp_fwd_trunk", NET_NERF, planes, lib.ptr(rays), lib.ptr(z), R, S, lib.ptr(packed), lib.ptr(raw), lib.ptr(work),
+             int(variant), _stream())
+    if ev:
+        ev[1].record()
+    return raw
+
+
+def live_list(raw: torch.Tensor, z: torch.Tensor, noise: Optional[torch.Tensor], noise_std: float, near_mask: float):
+    """lush_live_list: the points the compositing gives a non-zero alpha, from raw [R*S, 4] (sigma) and the noise it will add
+    -> (live_idx int32 [R*S], ray_start int32 [R+1], cnt int32 [2] = {length, R*S})."""
+    R, S = z.shape
+    dev, P = raw.device, R * S
+    lidx = torch.empty(P, dtype=torch.int32, device=dev)
+    ray_start = torch.empty(R + 1, dtype=torch.int32, device=dev)
+    cnt = torch.empty(2, dtype=torch.int32, device=dev)
+    aux = torch.empty(max(int(lib.load().lush_live_aux_bytes(P)), 4), dtype=torch.uint8, device=dev)
+    use_noise = noise is not None and noise_std > 0
+    lib.call("lush_live_list", lib.ptr(raw), lib.ptr(z), lib.ptr(noise) if use_noise else None, float(noise_std), float(near_mask), R, S,
+             lib.ptr(lidx), lib.ptr(ray_start), lib.ptr(cnt), lib.ptr(aux), _stream())
+    return lidx, ray_start, cnt
+
+
+def live_gather(draw: torch.Tensor, R: int, S: int, lidx: torch.Tensor, list_cnt: torch.Tensor):
+    """lush_live_gather: the d_raw rows of a list made in the forward, in list order -> (draw_c [R*S, 4], cnt int32 [2] = {non-zero rows, R*S})."""
+    draw_c = torch.empty(R * S, 4, dtype=torch.float32, device=draw.device)
+    cnt = torch.empty(2, dtype=torch.int32, device=draw.device)
+    lib.call("lush_live_gather", lib.ptr(draw), R, S, lib.ptr(lidx), lib.ptr(list_cnt), lib.ptr(draw_c), lib.ptr(cnt), _stream())
+    return draw_c, cnt
+
+
 def mlp_forward_live(net: int, planes: int, tensors, packed, rays, z, lidx, cnt, stash_planes: int = 0, variant: int = 0,
-                     timer: Optional[KernelTimer] = None):
+                     timer: Optional[KernelTimer] = None, raw: Optional[torch.Tensor] = None):
     """The forward once more, WITH the stash, on the live points of a pass (lush_mlp_fwd_live): returns the stash.  With a timer the
-    point count is read back (a synchronisation: the bench's kernel-group pass only)."""
+    point count is read back (a synchronisation: the bench's kernel-group pass only).  With `raw` [R*S, 4] the i-th point's row
+    is also written to raw[lidx[i]] (lush_mlp_fwd_live_raw: the forward of a march in the trunk form)."""
     R, S = z.shape
     sp = nplanes(stash_planes or planes)
     stash = torch.empty(lib.load().lush_mlp_stash_bytes(net, planes, sp, R * S), dtype=torch.uint8, device=rays.device)
@@ -223,8 +263,12 @@ def mlp_forward_live(net: int, planes: int, tensors, packed, rays, z, lidx, cnt,
     ev = timer.span("mlp_fwd" if net == NET_NERF else "noise_fwd", int(cnt[0].item())) if timer is not None else None
     if ev:
         ev[0].record()
-    lib.call("lush_mlp_fwd_live", net, planes, sp, lib.ptr(rays), lib.ptr(z), R, S, lib.ptr(packed), C.byref(st), lib.ptr(stash),
-             lib.ptr(lidx), lib.ptr(cnt), int(variant), _stream())
+    if raw is not None:
+        lib.call("lush_mlp_fwd_live_raw", net, planes, sp, lib.ptr(rays), lib.ptr(z), R, S, lib.ptr(packed), lib.ptr(stash),
+                 lib.ptr(lidx), lib.ptr(cnt), lib.ptr(raw), int(variant), _stream())
+    else:
+        lib.call("lush_mlp_fwd_live", net, planes, sp, lib.ptr(rays), lib.ptr(z), R, S, lib.ptr(packed), C.byref(st), lib.ptr(stash),
+                 lib.ptr(lidx), lib.ptr(cnt), int(variant), _stream())
     if ev:
         ev[1].record()
     return stash
@@ -419,7 +463,9 @@ class March(torch.autograd.Function):
 
     Outputs: rgb, depth, acc, density, raw, weights, z_vals [, rgb0, depth0, acc0, density0, z_std].
     density / raw / weights / z_vals / z_std are returned non-differentiable (raw, weights, z_vals are views of the workspace).
+    In the trunk form (include/lush_live_fwd.h: the headline mode's training march) raw carries rgb = 0 at samples of zero weight.
     """
+    fwd_list_kept = True      # False: no backward passes LUSH_MARCH_FWD_LIST_KEPT (tests compare the two forms of lush_march_bwd)
 
     @staticmethod
     def forward(ctx, batch, cfg: MarchCfg, draws: Dict[str, torch.Tensor], n_coarse: int, *params):
@@ -528,7 +574,13 @@ class March(torch.autograd.Function):
         R, fine_on = batch.shape[0], cfg.N_importance > 0
         c = March._c_cfg(cfg, R, ctx.same, True, ctx.packed)      # (the forward's packed buffers, not a second look at the hooks)
         c.variant = ctx.c_variant
-        gp = [_opt(g[0]), _opt(g[1]), _opt(g[2])] + ([_opt(g[7]), _opt(g[8]), _opt(g[9])] if fine_on else [None, None, None])
+        # The FIRST backward of a node finds the workspace as lush_march_fwd left it (the node owns it) and says so: the final pass
+        # then works on the forward's list and stash (include/lush_live_fwd.h).  Any later one (a retained graph) does not: the
+        # first one's coarse pass re-used the stash region.
+        if March.fwd_list_kept and not getattr(ctx, "fwd_list_spent", False) and lib.load().lush_march_trunk_form(C.byref(c)):
+            c.variant |= lib.MARCH_FWD_LIST_KEPT
+        ctx.fwd_list_spent = True
+        gp =[_opt(g[0]), _opt(g[1]), _opt(g[2])] + ([_opt(g[7]), _opt(g[8]), _opt(g[9])] if fine_on else [None, None, None])
         go = lib.MarchGout(*(None if t is None else t.data_ptr() for t in gp))
         any_main = any(t is not None for t in gp[:3])
         any_c = any(t is not None for t in gp[3:]) if fine_on else any_main
@@ -577,9 +629,23 @@ class March(torch.autograd.Function):
         ctx.live = live
         stash_fwd = need_grad and not live
         grp = "mlp_fwd_all" if live else "mlp_fwd"
+        # the trunk form of the one-call march (include/lush_live_fwd.h), piece by piece: the final pass runs trunk-only over all
+        # the points (timed as mlp_fwd_all), lists the points of non-zero alpha and runs the full forward with the stash on them
+        # (timed as mlp_fwd, where the one-call march's backward would otherwise run it)
+        trunk = live and bool(lib.load().lush_march_trunk_form(C.byref(March._c_cfg(cfg, batch.shape[0], same, need_grad))))
+        ctx.trunk = trunk
+        fwd_list = []
+
+        def fwd_pass(tensors, pk, z, final, noise):
+            if not (trunk and final):
+                return mlp_forward(NET_NERF, pf, tensors, pk, batch, z, stash_fwd, stash_code(pf, pb), var, tm, grp)
+            raw = mlp_forward_trunk(pf, pk, batch, z, var, tm, grp)
+            lidx, ray_start, cnt = live_list(raw, z, noise, cfg.raw_noise_std, cfg.near_mask)
+            fwd_list.extend((lidx, ray_start, cnt))
+            return raw, mlp_forward_live(NET_NERF, pf, tensors, pk, batch, z, lidx, cnt, stash_code(pf, pb), var, tm, raw=raw)
         zc = zgrid(batch, cfg.N_samples, cfg.lindisp, d.get("t_rand"))
         pk_c = mlp_pack(NET_NERF, pf, coarse, var)
-        raw_c, stash_c = mlp_forward(NET_NERF, pf, coarse, pk_c, batch, zc, stash_fwd, stash_code(pf, pb), var, tm, grp)
+        raw_c, stash_c = fwd_pass(coarse, pk_c, zc, cfg.N_importance == 0, d.get("noise_c"))
         rgb, depth, acc, weights, density = composite_fwd(raw_c, zc, batch, d.get("noise_c"), cfg,
                                                           lib.FAULT_COARSE_SHIFT if cfg.N_importance > 0 else 0)
         outs = [rgb, depth, acc, density]
@@ -588,7 +654,7 @@ class March(torch.autograd.Function):
         if cfg.N_importance > 0:
             zf, _, z_std = sample_merge(zc, weights, cfg.N_importance, d.get("u"), cfg.flags)
             pk_f = pk_c if same else mlp_pack(NET_NERF, pf, fine, var)
-            raw_f, stash_f = mlp_forward(NET_NERF, pf, fine, pk_f, batch, zf, stash_fwd, stash_code(pf, pb), var, tm, grp)
+            raw_f, stash_f = fwd_pass(fine, pk_f, zf, True, d.get("noise_f"))
             rgb1, depth1, acc1, weights1, density1 = composite_fwd(raw_f, zf, batch, d.get("noise_f"), cfg)
             outs = [rgb1, depth1, acc1, density1]
             saved += [zf, raw_f, stash_f if stash_f is not None else torch.empty(0, device=batch.device)]
@@ -601,7 +667,7 @@ class March(torch.autograd.Function):
             cfg.hooks.keep.update(stash_c=saved[2], stash_f=saved[5] if cfg.N_importance > 0 else None, P_c=zc.numel(),
                                   P_f=saved[3].numel() if cfg.N_importance > 0 else 0, batch=batch)
         ctx.fused = False
-        return outs, saved
+        return outs, saved + fwd_list      # (trunk form: the final pass's list, per-ray ranges and length, behind the passes' tensors)
 
     @staticmethod
     def _backward_piecewise(ctx, g, batch, saved, d, coarse, fine):
@@ -614,13 +680,21 @@ class March(torch.autograd.Function):
         grads_c: List[Optional[torch.Tensor]] = [None] * len(coarse)
         grads_f: List[Optional[torch.Tensor]] = []
 
-        def run(tensors, z, raw, noise, stash, gg):
+        # trunk form: the final pass (the first to run here) has its list and its stash from the forward
+        fwd_list = saved[-3:] if getattr(ctx, "trunk", False) else None
+
+        def run(tensors, z, raw, noise, stash, gg, final=False):
             draw = composite_bwd(raw, z, batch, noise, cfg, gg[0], gg[1], gg[2], drays)
             pk = mlp_pack(NET_NERF, pb, tensors, cfg.precision.variant)
             if getattr(ctx, "live", False):      # (the one-call march does the same inside lush_march_bwd)
-                lidx, draw_c, ray_start, cnt = live_compact(draw, z.shape[0], z.shape[1])
-                pk_f = pk if pf == pb else mlp_pack(NET_NERF, pf, tensors, cfg.precision.variant)      # (the forward's own fragments)
-                st_live = mlp_forward_live(NET_NERF, pf, tensors, pk_f, batch, z, lidx, cnt, stash_code(pf, pb), cfg.precision.variant, tm)
+                if final and fwd_list is not None:
+                    lidx, ray_start, cnt = fwd_list
+                    draw_c, _ = live_gather(draw, z.shape[0], z.shape[1], lidx, cnt)
+                    st_live = stash
+                else:
+                    lidx, draw_c, ray_start, cnt = live_compact(draw, z.shape[0], z.shape[1])
+                    pk_f = pk if pf == pb else mlp_pack(NET_NERF, pf, tensors, cfg.precision.variant)      # (the forward's own fragments)
+                    st_live = mlp_forward_live(NET_NERF, pf, tensors, pk_f, batch, z, lidx, cnt, stash_code(pf, pb), cfg.precision.variant, tm)
                 gr, dpts = mlp_backward(NET_NERF, stash_code(pf, pb), pb, tensors, pk, batch, z, draw_c, st_live,
                                         sink=grad_sink(tensors, cfg.hooks), variant=cfg.precision.variant, timer=tm, live=(lidx, cnt))
                 lib.call("lush_ray_grad_reduce_live", lib.ptr(dpts), lib.ptr(z), lib.ptr(lidx), lib.ptr(ray_start), z.shape[0], lib.ptr(drays), _stream())
@@ -631,9 +705,9 @@ class March(torch.autograd.Function):
             return gr
 
         if fine_on and any(x is not None for x in g_main):
-            grads_f = run(fine, saved[3], saved[4], d.get("noise_f"), saved[5], g_main)
+            grads_f = run(fine, saved[3], saved[4], d.get("noise_f"), saved[5], g_main, final=True)
         if any(x is not None for x in g_c):
-            grads_c = run(coarse, saved[0], saved[1], d.get("noise_c"), saved[2], g_c)
+            grads_c = run(coarse, saved[0], saved[1], d.get("noise_c"), saved[2], g_c, final=not fine_on)
         if fine_on and ctx.same and grads_f:
             grads_c = [(a + b if b is not None else a) if a is not None else b for a, b in zip(grads_c, grads_f)]
             grads_f = []
