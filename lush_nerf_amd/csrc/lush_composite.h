@@ -3,6 +3,7 @@
 // alpha, T and weights the forward computed, bit for bit.
 #pragma once
 #include "lush_common.h"
+#include <type_traits>
 
 namespace lush {
 
@@ -16,6 +17,13 @@ struct CompIn {
     float noise_std, near_mask;
     int white_bkgd;
 };
+// host: f(std::integral_constant<int, SPL>) for the SPL of a ray of S <= 256 samples
+template <class F>
+int comp_for_spl(int S, F&& f) {
+    if (S <= 64) return f(std::integral_constant<int, 1>{});
+    if (S <= 128) return f(std::integral_constant<int, 2>{});
+    return f(std::integral_constant<int, 4>{});
+}
 
 // The one statement of which samples before the last pass density on: the clamp of raw2outputs (pre = raw sigma + noise) and
 // near_mask.  A sample that fails it has density 0, alpha 0, weight 0 and an exactly zero d_raw row.  comp_load and the forward's

@@ -134,8 +134,6 @@ __global__ __launch_bounds__(RAYS_PER_BLOCK * 64) void composite_bwd_full_kernel
     if (lane < 3) d_rays_d[(long long)ray * 3 + lane] = norm > 0.f ? dnorm * c.rays[(long long)ray * 11 + 3 + lane] / norm : 0.f;
 }
 
-static inline int cdiv(long long a, long long b) { return (int)((a + b - 1) / b); }
-
 }  // namespace lush
 
 using namespace lush;
@@ -146,18 +144,14 @@ int lush_points_pack(const float* pts, const float* dirs, int R, int S, float* r
     if (R <= 0 || S <= 0) return set_error("lush_points_pack: empty");
     if (!pts || !dirs || !rays || !z) return set_error("lush_points_pack: points, directions and both outputs are required");
     if ((long long)R * S >= (1LL << 27)) return set_error("lush_points_pack: R * S must be below 2^27 points (what one MLP launch takes)");
-    hipLaunchKernelGGL(points_pack_kernel, dim3(cdiv((long long)R * S, 256)), dim3(256), 0, (hipStream_t)st, pts, dirs, R, S, rays, z);
-    LUSH_HIP(hipGetLastError());
-    return 0;
+    return launch(points_pack_kernel, dim3(cdiv((long long)R * S, 256)), dim3(256), 0, st, pts, dirs, R, S, rays, z);
 }
 
 int lush_points_grad(const float* dpts, int R, int S, float* d_pts, float* d_dirs, lush_stream_t st) {
     if (R <= 0 || S <= 0) return set_error("lush_points_grad: empty");
     if (!dpts || !d_pts || !d_dirs) return set_error("lush_points_grad: the d(point) rows and both outputs are required");
     if ((long long)R * S >= (1LL << 27)) return set_error("lush_points_grad: R * S must be below 2^27 points (what one MLP launch takes)");
-    hipLaunchKernelGGL(points_grad_kernel, dim3(cdiv(R, RAYS_PER_BLOCK)), dim3(RAYS_PER_BLOCK * 64), 0, (hipStream_t)st, dpts, R, S, d_pts, d_dirs);
-    LUSH_HIP(hipGetLastError());
-    return 0;
+    return launch(points_grad_kernel, dim3(cdiv(R, RAYS_PER_BLOCK)), dim3(RAYS_PER_BLOCK * 64), 0, st, dpts, R, S, d_pts, d_dirs);
 }
 
 int lush_composite_bwd_full(const float* raw, const float* z, const float* rays, int R, int S, const float* noise,
@@ -170,11 +164,8 @@ int lush_composite_bwd_full(const float* raw, const float* z, const float* rays,
     const CompIn c{raw, z, rays, noise, R, S, noise_std, near_mask, white_bkgd};
     const CompGrads g{g_rgb, g_density, g_acc, g_weights, g_depth};
     const dim3 grid(cdiv(R, RAYS_PER_BLOCK)), block(RAYS_PER_BLOCK * 64);
-    if (S <= 64) hipLaunchKernelGGL(composite_bwd_full_kernel<1>, grid, block, 0, (hipStream_t)st, c, g, d_raw, d_z, d_rays_d);
-    else if (S <= 128) hipLaunchKernelGGL(composite_bwd_full_kernel<2>, grid, block, 0, (hipStream_t)st, c, g, d_raw, d_z, d_rays_d);
-    else hipLaunchKernelGGL(composite_bwd_full_kernel<4>, grid, block, 0, (hipStream_t)st, c, g, d_raw, d_z, d_rays_d);
-    LUSH_HIP(hipGetLastError());
-    return 0;
+    return comp_for_spl(S, [&](auto spl) {
+        return launch(composite_bwd_full_kernel<decltype(spl)::value>, grid, block, 0, st, c, g, d_raw, d_z, d_rays_d); });
 }
 
 }  // extern "C"

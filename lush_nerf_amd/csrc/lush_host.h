@@ -15,6 +15,17 @@ int set_hip_error(hipError_t e, const char* what, const char* file, int line);
         if (_e != hipSuccess) return ::lush::set_hip_error(_e, #expr, __FILE__, __LINE__); \
     } while (0)
 
+inline int cdiv(long long a, long long b) { return (int)((a + b - 1) / b); }
+
+// What every C entry point of the ray-level files ends in: the launch (arguments converted to the kernel's parameter types),
+// then the launch's own error.  (The MLP launchers set an LDS attribute once per device first: KernelOnce below.)
+template <class... KA, class... A>
+int launch(void (*k)(KA...), dim3 grid, dim3 block, size_t lds, lush_stream_t st, A&&... a) {
+    hipLaunchKernelGGL(k, grid, block, lds, (hipStream_t)st, static_cast<KA>(a)...);
+    LUSH_HIP(hipGetLastError());
+    return 0;
+}
+
 // Launch set-up that is safe with several devices and several host threads in one process (the
 // reference calls this path from one DataParallel worker thread per GPU): nothing here is keyed by "the first device
 // that happened to call".  current_device_cus: CU count of the CALLING thread's current device (cached per device id);

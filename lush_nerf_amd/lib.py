@@ -17,8 +17,9 @@ from . import abi
 HERE = os.path.dirname(os.path.abspath(__file__))
 CSRC = os.path.join(HERE, "csrc")
 SO_PATH = os.path.join(HERE, "liblush_march.so")      # (developer tools load another build with use_library(path) BEFORE load())
-SOURCES = ["lush_march.hip", "lush_mlp.hip", "lush_mlp_chain.hip", "lush_mlp_wide.hip", "lush_mlp_wide_bwd.hip", "lush_abi.hip", "lush_march_abi.hip", "lush_field.hip"]
-HEADERS = ["lush_common.h", "lush_composite.h", "lush_mlp.h", "lush_mlp_dev.h", "lush_mlp_wide.h", "lush_host.h", os.path.join("..", "..", "include", "lush_live_fwd.h"),
+SOURCES = ["lush_march.hip", "lush_mlp.hip", "lush_mlp_chain.hip", "lush_mlp_wide.hip", "lush_mlp_wide_bwd.hip", "lush_abi.hip", "lush_march_abi.hip", "lush_field.hip",
+           "lush_rays.hip", "lush_rbk.hip", "lush_image.hip", "lush_step.hip"]
+HEADERS = ["lush_common.h", "lush_composite.h", "lush_rays.h", "lush_mlp.h", "lush_mlp_dev.h", "lush_mlp_wide.h", "lush_host.h", os.path.join("..", "..", "include", "lush_live_fwd.h"),
            os.path.join("..", "..", "include", "lush_subframe.h"),
            os.path.join("..", "..", "include", "lush_march.h")]      # (the last one is the contract _abi is read from)
 
