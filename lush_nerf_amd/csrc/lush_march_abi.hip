@@ -8,6 +8,7 @@
 #include "lush_host.h"
 #include "../../include/lush_march.h"
 #include "../../include/lush_live_fwd.h"
+#include "../../include/lush_live_coarse.h"
 
 using namespace lush;
 
@@ -25,6 +26,7 @@ struct Layout {
     size_t pkbc, pkbf;                           // packed weights of the backward when its plane code differs
     size_t draw, dstash, dpts;                   // backward scratch, shared by the passes (they run one after the other)
     size_t live_idx, draw_c, ray_start, live_cnt, live_aux;     // live-point backward (round 5): the list, its d_raw rows, per-ray ranges, count, scan scratch
+    size_t live_idx_c, ray_start_c;              // the coarse pass's list and per-ray ranges: its own in the coarse trunk form, else the ones above
     size_t total;
     size_t stashc_bytes, stashf_bytes;
     bool live;                                   // the backward re-runs the forward on the live points (the forward call keeps no stash)
@@ -46,6 +48,12 @@ inline bool trunk_form(const lush_march_cfg* c) {
     return live_mode(c) && c->planes_fwd == PLANES_F16 && !(c->variant & (LUSH_VARIANT_FWD_HALF | LUSH_VARIANT_FWD_512 | LUSH_VARIANT_PE_ROWS));
 }
 
+// The coarse pass of a march with a fine pass in the same form (include/lush_live_coarse.h): asked for by a bit of the word, since
+// the coarse stash must then survive the fine pass and takes a region of its own.
+inline bool coarse_trunk_form(const lush_march_cfg* c) {
+    return (c->variant & LUSH_MARCH_COARSE_TRUNK) && c->N_importance > 0 && trunk_form(c);
+}
+
 bool layout(const lush_march_cfg* c, Layout& L) {
     if (!c || c->R <= 0 || c->N_samples < 2 || c->N_importance < 0) return false;
     const long long R = c->R, S = c->N_samples, Ni = c->N_importance, Sf = S + Ni;
@@ -65,7 +73,10 @@ bool layout(const lush_march_cfg* c, Layout& L) {
     // inference kernels' scratch), its backward re-runs the forward with the stash pass by pass, fine first, and a pass is done with
     // its stash before the next one starts: the coarse pass's region is the head of the fine pass's (-4.4 KB per coarse point of
     // workspace: 5.8 GB at BASELINE config 2).
-    const bool share_stash = L.live && Ni > 0;
+    // The coarse trunk form is the exception: its forward writes the live coarse rows' stash, which the backward's coarse pass reads
+    // after the fine pass has come and gone.
+    const bool coarse_own = coarse_trunk_form(c);
+    const bool share_stash = L.live && Ni > 0 && !coarse_own;
     if (!share_stash) L.stashc = take(L.stashc_bytes);
     if (Ni > 0) {
         L.zf = take(R * Sf * 4); L.zs = take(R * Ni * 4); L.wf = take(R * Sf * 4); L.rawf = take(R * Sf * 16);
@@ -87,6 +98,8 @@ bool layout(const lush_march_cfg* c, Layout& L) {
             L.ray_start = take(((size_t)R + 1) * 4);
             L.live_cnt = take(256);
             L.live_aux = take(lush_live_aux_bytes(Pmax));
+            L.live_idx_c = coarse_own ? take(R * S * 4) : L.live_idx;
+            L.ray_start_c = coarse_own ? take(((size_t)R + 1) * 4) : L.ray_start;
         }
     }
     L.total = off;
@@ -128,6 +141,11 @@ int lush_march_trunk_form(const lush_march_cfg* cfg) {
     return layout(cfg, L) && trunk_form(cfg) ? 1 : 0;
 }
 
+int lush_march_coarse_trunk_form(const lush_march_cfg* cfg) {
+    Layout L;
+    return layout(cfg, L) && coarse_trunk_form(cfg) ? 1 : 0;
+}
+
 int lush_march_fwd(const lush_march_cfg* cfg, const float* rays, const lush_mlp_params* coarse, const lush_mlp_params* fine,
                    const lush_march_draws* draws, const lush_march_out* out, void* workspace, int* flags, lush_stream_t st) {
     Layout L;
@@ -140,7 +158,7 @@ int lush_march_fwd(const lush_march_cfg* cfg, const float* rays, const lush_mlp_
     if (two && (!out->rgb0 || !out->depth0 || !out->acc0 || !out->density0 || !out->z_std)) return set_error("lush_march_fwd: the coarse outputs and z_std are required when N_importance > 0");
     const lush_mlp_params* pfine = cfg->same_net ? coarse : fine;
     char* w = (char*)workspace;
-    const int pf = cfg->planes_fwd, var = cfg->variant;
+    const int pf = cfg->planes_fwd, var = cfg->variant & LUSH_VARIANT_KERNEL_BITS;      // (what the launchers see: no layout or permission bit)
     const int sc = L.live ? 0 : stash_code(pf, cfg->planes_bwd);      // live-point backward: the forward keeps raw, z, weights only
     const float* t_rand = draws && cfg->perturb > 0.f ? draws->t_rand : nullptr;
     const float* noise_c = draws && cfg->raw_noise_std > 0.f ? draws->noise_c : nullptr;
@@ -149,15 +167,18 @@ int lush_march_fwd(const lush_march_cfg* cfg, const float* rays, const lush_mlp_
     // the MLP forward of a pass.  The final pass in the trunk form: sigma of every point, the list of the points whose alpha is
     // not zero (into the backward's list regions; its length beside the LIVE_COUNTS words), all of the net WITH the stash on the
     // list, which writes their rows.  A row the list leaves out keeps rgb = 0: finite, and multiplied by a weight of exactly 0.
-    const bool trunk = trunk_form(cfg);
+    // The coarse pass ahead of a fine one runs the same way in the coarse trunk form (include/lush_live_coarse.h), with its own
+    // stash, list and ranges and its own count word; the scan scratch serves one list after the other.
+    const bool trunk = trunk_form(cfg), trunk_c = coarse_trunk_form(cfg);
     auto mlp = [&](bool final_pass, const float* z, int Sp, const void* pk, const lush_mlp_params* prm, size_t rawoff, size_t stashoff, const float* noise) -> int {
         float* raw = (float*)(w + rawoff);
-        if (!(trunk && final_pass)) return lush_mlp_fwd(0, pf, sc, rays, z, R, Sp, pk, prm, raw, w + stashoff, var, st);
-        int* lidx = (int*)(w + L.live_idx);
-        int* list_cnt = (int*)(w + L.live_cnt) + LUSH_LIVE_LIST_COUNT_WORD;
+        if (!(final_pass ? trunk : trunk_c)) return lush_mlp_fwd(0, pf, sc, rays, z, R, Sp, pk, prm, raw, w + stashoff, var, st);
+        int* lidx = (int*)(w + (final_pass ? L.live_idx : L.live_idx_c));
+        int* ray_start = (int*)(w + (final_pass ? L.ray_start : L.ray_start_c));
+        int* list_cnt = (int*)(w + L.live_cnt) + (final_pass ? LUSH_LIVE_LIST_COUNT_WORD : LUSH_LIVE_COARSE_LIST_COUNT_WORD);
         int r = lush_mlp_fwd_trunk(0, pf, rays, z, R, Sp, pk, raw, w + stashoff, var, st);
         if (r) return r;
-        r = lush_live_list(raw, z, noise, cfg->raw_noise_std, cfg->near_mask, R, Sp, lidx, (int*)(w + L.ray_start), list_cnt, w + L.live_aux, st);
+        r = lush_live_list(raw, z, noise, cfg->raw_noise_std, cfg->near_mask, R, Sp, lidx, ray_start, list_cnt, w + L.live_aux, st);
         if (r) return r;
         return lush_mlp_fwd_live_raw(0, pf, stash_code(pf, cfg->planes_bwd), rays, z, R, Sp, pk, w + stashoff, lidx, list_cnt, raw, var, st);
     };
@@ -167,7 +188,7 @@ int lush_march_fwd(const lush_march_cfg* cfg, const float* rays, const lush_mlp_
     // weights: packed by the caller once per step (cfg->packed_*), or here into the workspace
     const void* pkc = cfg->packed_coarse;
     if (!pkc) {
-        rc = lush_mlp_pack_for(0, pf, coarse, w + L.pkc, cfg->variant, st);
+        rc = lush_mlp_pack_for(0, pf, coarse, w + L.pkc, var, st);
         if (rc) return rc;
         pkc = w + L.pkc;
     }
@@ -183,7 +204,7 @@ int lush_march_fwd(const lush_march_cfg* cfg, const float* rays, const lush_mlp_
     if (rc) return rc;
     const void* pkf = cfg->same_net ? pkc : cfg->packed_fine;
     if (!pkf) {
-        rc = lush_mlp_pack_for(0, pf, pfine, w + L.pkf, cfg->variant, st);
+        rc = lush_mlp_pack_for(0, pf, pfine, w + L.pkf, var, st);
         if (rc) return rc;
         pkf = w + L.pkf;
     }
@@ -212,6 +233,12 @@ int lush_march_bwd(const lush_march_cfg* cfg, const float* rays, const lush_mlp_
     // forward's list and stash (include/lush_live_fwd.h).  Read here, before `var` loses what is no kernel bit; without the bit
     // every pass lists its live points and re-runs the forward on them, which is correct after any forward.
     const bool kept = (cfg->variant & LUSH_MARCH_FWD_LIST_KEPT) && trunk_form(cfg);
+    // Where a pass keeps its list and per-ray ranges, and the word that holds the length of the list its forward made.  One set of
+    // regions serves both passes, except in the coarse trunk form (include/lush_live_coarse.h), whose coarse pass has its own.
+    struct PassList { size_t idx, ray_start; int fwd_word; };
+    const PassList list_f{L.live_idx, L.ray_start, LUSH_LIVE_LIST_COUNT_WORD};
+    const bool trunk_c = coarse_trunk_form(cfg);
+    const PassList list_c = trunk_c ? PassList{L.live_idx_c, L.ray_start_c, LUSH_LIVE_COARSE_LIST_COUNT_WORD} : list_f;
     // One pass = compositing backward, (re-pack), gradient chain, d(point) -> d(ray), weight gradients; the fine pass first,
     // then the coarse one (which does not depend on it: z_samples are detached, models/lushnerf.py:546), all on the caller's
     // stream out of one backward scratch.  (Round 3 ran the fine pass's weight gradients on a second stream beside the coarse
@@ -223,7 +250,7 @@ int lush_march_bwd(const lush_march_cfg* cfg, const float* rays, const lush_mlp_
     // fragments of the backward's plane code: the caller's (cfg->packed_*), else the forward's copy in the workspace when the
     // codes agree, else packed here
     auto chain = [&](const lush_mlp_params* prm, size_t zoff, size_t rawoff, size_t stashoff, const void* pk_ready, size_t pkboff, bool repack,
-                     int Sp, const float* noise, const float* g_rgb, const float* g_depth, const float* g_acc, const void* pk_fwd, int slot, bool from_fwd) -> int {
+                     int Sp, const float* noise, const float* g_rgb, const float* g_depth, const float* g_acc, const void* pk_fwd, int slot, bool from_fwd, const PassList& pl) -> int {
         const float* z = (const float*)(w + zoff);
         // the compositing backward also leaves the per-workgroup maxima of |d_raw| (in the d(point) array, which the chain only
         // writes afterwards) for the fp16 chain's loss scale, zeroes the weight-gradient scratch and, in the march's first pass,
@@ -243,7 +270,7 @@ int lush_march_bwd(const lush_march_cfg* cfg, const float* rays, const lush_mlp_
         const void* pk = pk_ready;
         if (!pk) {
             if (repack) {       // the backward computes with another plane code than the forward: its own fragments
-                rc = lush_mlp_pack_for(0, pb, prm, w + pkboff, cfg->variant, st);
+                rc = lush_mlp_pack_for(0, pb, prm, w + pkboff, var, st);
                 if (rc) return rc;
             }
             pk = w + pkboff;
@@ -251,18 +278,19 @@ int lush_march_bwd(const lush_march_cfg* cfg, const float* rays, const lush_mlp_
         if (L.live) {
             // the live points of this pass: list, gathered d_raw rows, per-ray ranges (three small launches); the forward once
             // more, WITH the stash, on the list; then chain and d(ray) on `cnt` points (read on the device)
-            int* lidx = (int*)(w + L.live_idx);
+            int* lidx = (int*)(w + pl.idx);
+            int* ray_start = (int*)(w + pl.ray_start);
             int* lcnt = (int*)(w + L.live_cnt) + 2 * slot;      // {live points, points} of the fine (slot 0) / coarse (slot 1) pass: LUSH_VIEW_LIVE_COUNTS
             float* draw_c = (float*)(w + L.draw_c);
             const int* len = lcnt;               // the length of the list the launches below run on
             if (from_fwd) {
                 // the forward's list, per-ray ranges and stash stand: d_raw rows in list order (a listed point may have a zero row:
                 // it adds exact zeros), and the count of the non-zero ones for LIVE_COUNTS
-                len = (const int*)(w + L.live_cnt) + LUSH_LIVE_LIST_COUNT_WORD;
+                len = (const int*)(w + L.live_cnt) + pl.fwd_word;
                 rc = lush_live_gather(x.draw, R, Sp, lidx, len, draw_c, lcnt, st);
                 if (rc) return rc;
             } else {
-                rc = lush_live_compact(x.draw, R, Sp, lidx, draw_c, (int*)(w + L.ray_start), lcnt, w + L.live_aux, st);
+                rc = lush_live_compact(x.draw, R, Sp, lidx, draw_c, ray_start, lcnt, w + L.live_aux, st);
                 if (rc) return rc;
                 const void* pkf = pk_fwd;            // forward fragments: the caller's buffer or the forward call's copy in the workspace
                 rc = lush_mlp_fwd_live(0, pf, sc, rays, z, R, Sp, pkf, prm, w + stashoff, lidx, lcnt, var, st);
@@ -270,15 +298,15 @@ int lush_march_bwd(const lush_march_cfg* cfg, const float* rays, const lush_mlp_
             }
             rc = mlp_bwd_chain_prepared(0, sc, pb, rays, z, R, Sp, pk, prm, draw_c, w + stashoff, x.dstash, x.dpts, var, (hipStream_t)st, lidx, len);
             if (rc) return rc;
-            return lush_ray_grad_reduce_live(x.dpts, z, lidx, (const int*)(w + L.ray_start), R, drays, st);
+            return lush_ray_grad_reduce_live(x.dpts, z, lidx, ray_start, R, drays, st);
         }
         rc = mlp_bwd_chain_prepared(0, sc, pb, rays, z, R, Sp, pk, prm, x.draw, w + stashoff, x.dstash, x.dpts, var, (hipStream_t)st);
         if (rc) return rc;
         return lush_ray_grad_reduce(x.dpts, z, R, Sp, drays, st);
     };
-    auto weights = [&](const lush_mlp_params* prm, const lush_mlp_grads* gr, size_t stashoff, int Sp, int slot, bool from_fwd) -> int {
+    auto weights = [&](const lush_mlp_params* prm, const lush_mlp_grads* gr, size_t stashoff, int Sp, int slot, bool from_fwd, const PassList& pl) -> int {
         if (L.live) return mlp_bwd_weights_prepared(0, sc, pb, R, Sp, prm, (const float*)(w + L.draw_c), w + stashoff, x.dstash, gr, var, (hipStream_t)st,
-                                                    (const int*)(w + L.live_cnt) + (from_fwd ? LUSH_LIVE_LIST_COUNT_WORD : 2 * slot));
+                                                    (const int*)(w + L.live_cnt) + (from_fwd ? pl.fwd_word : 2 * slot));
         return mlp_bwd_weights_prepared(0, sc, pb, R, Sp, prm, x.draw, w + stashoff, x.dstash, gr, var, (hipStream_t)st);
     };
     const bool any_main = g->rgb || g->depth || g->acc;
@@ -292,17 +320,19 @@ int lush_march_bwd(const lush_march_cfg* cfg, const float* rays, const lush_mlp_
     const void* ready_f = cfg->same_net ? ready_c : (pb == pf ? cfg->packed_fine : cfg->packed_bwd_fine);
     if (two && any_main) {
         rc = chain(pfine, L.zf, L.rawf, L.stashf, ready_f, L.pkbf, pb != pf, Sf, noise_f, g->rgb, g->depth, g->acc,
-                   cfg->same_net ? (cfg->packed_coarse ? cfg->packed_coarse : (const void*)(w + L.pkc)) : (cfg->packed_fine ? cfg->packed_fine : (const void*)(w + L.pkf)), 0, kept);
+                   cfg->same_net ? (cfg->packed_coarse ? cfg->packed_coarse : (const void*)(w + L.pkc)) : (cfg->packed_fine ? cfg->packed_fine : (const void*)(w + L.pkf)), 0, kept, list_f);
         if (rc) return rc;
         packed_b_c = cfg->same_net && pb != pf;     // the shared net's backward fragments are packed now
-        rc = weights(pfine, gfine, L.stashf, Sf, 0, kept);
+        rc = weights(pfine, gfine, L.stashf, Sf, 0, kept, list_f);
         if (rc) return rc;
     }
+    // the coarse pass: the only one, it is the final pass; ahead of a fine one it has a forward's list in the coarse trunk form alone
+    const bool kept_c = kept && (!two || trunk_c);
     if (any_c) {
         rc = chain(coarse, L.zc, L.rawc, L.stashc, ready_c, L.pkbc, pb != pf && !packed_b_c, S, noise_c, two ? g->rgb0 : g->rgb,
-                   two ? g->depth0 : g->depth, two ? g->acc0 : g->acc, cfg->packed_coarse ? cfg->packed_coarse : (const void*)(w + L.pkc), two ? 1 : 0, kept && !two);
+                   two ? g->depth0 : g->depth, two ? g->acc0 : g->acc, cfg->packed_coarse ? cfg->packed_coarse : (const void*)(w + L.pkc), two ? 1 : 0, kept_c, list_c);
         if (rc) return rc;
-        rc = weights(coarse, g_coarse, L.stashc, S, two ? 1 : 0, kept && !two);
+        rc = weights(coarse, g_coarse, L.stashc, S, two ? 1 : 0, kept_c, list_c);
     }
     return rc;
 }

@@ -3,7 +3,8 @@
 The shared object is built IN-TREE by ``build()`` (hipcc --offload-arch=gfx950)
 and loaded with ctypes.  There is no fallback: if the library is missing or a
 call fails the product raises.  Signatures, structs and constants are read from include/lush_march.h (abi.py), the one
-later entry point from the second contract header include/lush_subframe.h, the trunk form's from the third, include/lush_live_fwd.h.
+later entry point from the second contract header include/lush_subframe.h, the trunk form's from the third, include/lush_live_fwd.h,
+the coarse pass's trunk form from the fourth, include/lush_live_coarse.h.
 """
 from __future__ import annotations
 
@@ -19,7 +20,8 @@ CSRC = os.path.join(HERE, "csrc")
 SO_PATH = os.path.join(HERE, "liblush_march.so")      # (developer tools load another build with use_library(path) BEFORE load())
 SOURCES = ["lush_march.hip", "lush_mlp.hip", "lush_mlp_chain.hip", "lush_mlp_wide.hip", "lush_mlp_wide_bwd.hip", "lush_abi.hip", "lush_march_abi.hip", "lush_field.hip",
            "lush_rays.hip", "lush_rbk.hip", "lush_image.hip", "lush_step.hip"]
-HEADERS = ["lush_common.h", "lush_composite.h", "lush_rays.h", "lush_mlp.h", "lush_mlp_dev.h", "lush_mlp_wide.h", "lush_host.h", os.path.join("..", "..", "include", "lush_live_fwd.h"),
+HEADERS = ["lush_common.h", "lush_composite.h", "lush_rays.h", "lush_mlp.h", "lush_mlp_dev.h", "lush_mlp_wide.h", "lush_host.h", os.path.join("..", "..", "include", "lush_live_coarse.h"),
+           os.path.join("..", "..", "include", "lush_live_fwd.h"),
            os.path.join("..", "..", "include", "lush_subframe.h"),
            os.path.join("..", "..", "include", "lush_march.h")]      # (the last one is the contract _abi is read from)
 
@@ -144,6 +146,13 @@ _SIGS_LIVE_FWD = _abi_live_fwd.protos
 EXPORTS_LIVE_FWD = list(_SIGS_LIVE_FWD)
 MARCH_FWD_LIST_KEPT = _abi_live_fwd.consts["LUSH_MARCH_FWD_LIST_KEPT"]
 LIVE_LIST_COUNT_WORD = _abi_live_fwd.consts["LUSH_LIVE_LIST_COUNT_WORD"]
+# The fourth, include/lush_live_coarse.h: the configuration bit that gives the coarse pass the same form (a stash and list regions of
+# its own in the workspace), the word of its list's length and the predicate lush_march_coarse_trunk_form
+_abi_live_coarse = abi.parse(open(os.path.join(CSRC, HEADERS[-4])).read(), "lush_live_coarse.h")
+_SIGS_LIVE_COARSE = _abi_live_coarse.protos
+EXPORTS_LIVE_COARSE = list(_SIGS_LIVE_COARSE)
+MARCH_COARSE_TRUNK = _abi_live_coarse.consts["LUSH_MARCH_COARSE_TRUNK"]
+LIVE_COARSE_LIST_COUNT_WORD = _abi_live_coarse.consts["LUSH_LIVE_COARSE_LIST_COUNT_WORD"]
 
 
 def fault_names(word: int):
@@ -162,7 +171,7 @@ def load():
         raise RuntimeError(f"{SO_PATH} is missing: run `python -c 'import __graft_entry__ as g; g.build()'` "
                            "(the HIP extension is required; there is no fallback path)")
     lib = C.CDLL(SO_PATH)
-    for name, (args, res) in (*_SIGS.items(), *_SIGS_SUBFRAME.items(), *_SIGS_LIVE_FWD.items()):
+    for name, (args, res) in (*_SIGS.items(), *_SIGS_SUBFRAME.items(), *_SIGS_LIVE_FWD.items(), *_SIGS_LIVE_COARSE.items()):
         fn = getattr(lib, name)
         fn.argtypes = args
         fn.restype = res

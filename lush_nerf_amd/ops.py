@@ -464,8 +464,11 @@ class March(torch.autograd.Function):
     Outputs: rgb, depth, acc, density, raw, weights, z_vals [, rgb0, depth0, acc0, density0, z_std].
     density / raw / weights / z_vals / z_std are returned non-differentiable (raw, weights, z_vals are views of the workspace).
     In the trunk form (include/lush_live_fwd.h: the headline mode's training march) raw carries rgb = 0 at samples of zero weight.
+    With a fine pass that march also runs its coarse pass in the form (include/lush_live_coarse.h: LUSH_MARCH_COARSE_TRUNK, a coarse
+    stash and list of their own in the workspace, +4.9 KB per coarse point); `coarse_trunk = False` keeps the shared region.
     """
     fwd_list_kept = True      # False: no backward passes LUSH_MARCH_FWD_LIST_KEPT (tests compare the two forms of lush_march_bwd)
+    coarse_trunk = True       # False: no march asks for LUSH_MARCH_COARSE_TRUNK (include/lush_live_coarse.h; tests compare with and without)
 
     @staticmethod
     def forward(ctx, batch, cfg: MarchCfg, draws: Dict[str, torch.Tensor], n_coarse: int, *params):
@@ -527,6 +530,18 @@ class March(torch.autograd.Function):
         return c
 
     @staticmethod
+    def _ask_coarse_trunk(c) -> bool:
+        """Set LUSH_MARCH_COARSE_TRUNK in c.variant where the library runs the configuration in that form (include/lush_live_coarse.h:
+        the coarse pass, too, computes colour on live points only, out of a stash and list regions of its own); says whether it did."""
+        if not March.coarse_trunk:
+            return False
+        c.variant |= lib.MARCH_COARSE_TRUNK
+        if lib.load().lush_march_coarse_trunk_form(C.byref(c)):
+            return True
+        c.variant &= ~lib.MARCH_COARSE_TRUNK
+        return False
+
+    @staticmethod
     def _view(ws, c, which, shape):
         off, nbytes = C.c_size_t(), C.c_size_t()
         lib.call("lush_march_view", C.byref(c), which, C.byref(off), C.byref(nbytes))
@@ -538,6 +553,7 @@ class March(torch.autograd.Function):
         Sl = S + Ni
         ctx.packed = March._packed_of(cfg, same, need_grad, coarse, fine)
         c = March._c_cfg(cfg, R, same, need_grad, ctx.packed)
+        March._ask_coarse_trunk(c)
         ctx.c_variant = int(c.variant)          # (the backward must lay the workspace out as the forward did)
         nbytes = lib.load().lush_march_workspace_bytes(C.byref(c))
         if nbytes == 0:
@@ -632,16 +648,19 @@ class March(torch.autograd.Function):
         # the trunk form of the one-call march (include/lush_live_fwd.h), piece by piece: the final pass runs trunk-only over all
         # the points (timed as mlp_fwd_all), lists the points of non-zero alpha and runs the full forward with the stash on them
         # (timed as mlp_fwd, where the one-call march's backward would otherwise run it)
-        trunk = live and bool(lib.load().lush_march_trunk_form(C.byref(March._c_cfg(cfg, batch.shape[0], same, need_grad))))
-        ctx.trunk = trunk
+        # In the coarse trunk form (include/lush_live_coarse.h) the coarse pass ahead of a fine one runs the same way.
+        c = March._c_cfg(cfg, batch.shape[0], same, need_grad)
+        trunk = live and bool(lib.load().lush_march_trunk_form(C.byref(c)))
+        trunk_c = trunk and March._ask_coarse_trunk(c)
+        ctx.trunk, ctx.trunk_c = trunk, trunk_c
         fwd_list = []
 
         def fwd_pass(tensors, pk, z, final, noise):
-            if not (trunk and final):
+            if not (trunk if final else trunk_c):
                 return mlp_forward(NET_NERF, pf, tensors, pk, batch, z, stash_fwd, stash_code(pf, pb), var, tm, grp)
             raw = mlp_forward_trunk(pf, pk, batch, z, var, tm, grp)
             lidx, ray_start, cnt = live_list(raw, z, noise, cfg.raw_noise_std, cfg.near_mask)
-            fwd_list.extend((lidx, ray_start, cnt))
+            fwd_list.extend((lidx, ray_start, cnt))      # (the coarse pass's first when both passes list)
             return raw, mlp_forward_live(NET_NERF, pf, tensors, pk, batch, z, lidx, cnt, stash_code(pf, pb), var, tm, raw=raw)
         zc = zgrid(batch, cfg.N_samples, cfg.lindisp, d.get("t_rand"))
         pk_c = mlp_pack(NET_NERF, pf, coarse, var)
@@ -667,7 +686,7 @@ class March(torch.autograd.Function):
             cfg.hooks.keep.update(stash_c=saved[2], stash_f=saved[5] if cfg.N_importance > 0 else None, P_c=zc.numel(),
                                   P_f=saved[3].numel() if cfg.N_importance > 0 else 0, batch=batch)
         ctx.fused = False
-        return outs, saved + fwd_list      # (trunk form: the final pass's list, per-ray ranges and length, behind the passes' tensors)
+        return outs, saved + fwd_list      # (trunk form: a pass's list, per-ray ranges and length, behind the passes' tensors)
 
     @staticmethod
     def _backward_piecewise(ctx, g, batch, saved, d, coarse, fine):
@@ -680,14 +699,17 @@ class March(torch.autograd.Function):
         grads_c: List[Optional[torch.Tensor]] = [None] * len(coarse)
         grads_f: List[Optional[torch.Tensor]] = []
 
-        # trunk form: the final pass (the first to run here) has its list and its stash from the forward
-        fwd_list = saved[-3:] if getattr(ctx, "trunk", False) else None
+        # trunk form: the final pass (the first to run here) has its list and its stash from the forward; in the coarse trunk form
+        # the coarse pass ahead of it has, too (saved in front of the final pass's)
+        fwd_list_final = saved[-3:] if getattr(ctx, "trunk", False) else None
+        fwd_list_coarse = saved[-6:-3] if getattr(ctx, "trunk_c", False) else None
 
         def run(tensors, z, raw, noise, stash, gg, final=False):
+            fwd_list = fwd_list_final if final else fwd_list_coarse
             draw = composite_bwd(raw, z, batch, noise, cfg, gg[0], gg[1], gg[2], drays)
             pk = mlp_pack(NET_NERF, pb, tensors, cfg.precision.variant)
             if getattr(ctx, "live", False):      # (the one-call march does the same inside lush_march_bwd)
-                if final and fwd_list is not None:
+                if fwd_list is not None:
                     lidx, ray_start, cnt = fwd_list
                     draw_c, _ = live_gather(draw, z.shape[0], z.shape[1], lidx, cnt)
                     st_live = stash
