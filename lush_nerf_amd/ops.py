@@ -451,6 +451,27 @@ def _flat_grads(tensors, dev):
     return views
 
 
+@dataclass
+class _PiecePass:
+    """What the piecewise march keeps of one pass for its backward.  fwd_list = (lidx, ray_start, cnt) of the list the pass's forward
+    made (the trunk form: the stash is then the listed points'), else None: its backward lists for itself."""
+    z: torch.Tensor
+    raw: torch.Tensor
+    stash: torch.Tensor                       # empty where the forward kept none (a live-point backward outside the trunk form)
+    fwd_list: Optional[tuple] = None
+
+    @staticmethod
+    def flatten(passes):
+        """For save_for_backward: z, raw, stash of every pass, then the lists of the passes that made one (the coarse pass's first)."""
+        return [t for p in passes for t in (p.z, p.raw, p.stash)] + [t for p in passes if p.fwd_list is not None for t in p.fwd_list]
+
+    @staticmethod
+    def rebuild(saved, has_list):
+        """The passes back from what flatten() saved; has_list[i]: pass i made a list."""
+        lists = iter(saved[3 * len(has_list):])
+        return [_PiecePass(*saved[3 * i:3 * i + 3], tuple(next(lists) for _ in range(3)) if h else None) for i, h in enumerate(has_list)]
+
+
 class March(torch.autograd.Function):
     """NeRFAll.render_rays_nonoise (models/lushnerf.py:481-583) as one differentiable op:
     z grid + jitter -> coarse MLP -> compositing -> sample_pdf + merge -> fine MLP ->
@@ -542,10 +563,21 @@ class March(torch.autograd.Function):
         return False
 
     @staticmethod
-    def _view(ws, c, which, shape):
+    def _view_bytes(ws, c, which):
+        """The bytes of the workspace that lush_march_view calls `which` (lib.VIEW_*)."""
         off, nbytes = C.c_size_t(), C.c_size_t()
         lib.call("lush_march_view", C.byref(c), which, C.byref(off), C.byref(nbytes))
-        return ws[off.value:off.value + nbytes.value].view(torch.float32).view(*shape)
+        return ws[off.value:off.value + nbytes.value]
+
+    @staticmethod
+    def _view(ws, c, which, shape):
+        return March._view_bytes(ws, c, which).view(torch.float32).view(*shape)
+
+    @staticmethod
+    def _c_args(d, coarse, fine):
+        """(lush_march_draws, the coarse net's lush_mlp_params, the fine net's) as lush_march_fwd and lush_march_bwd take them."""
+        dr = lib.MarchDraws(*(None if d.get(k) is None else d[k].data_ptr() for k in ("t_rand", "noise_c", "u", "noise_f")))
+        return dr, lib.mlp_struct(coarse, _NL[NET_NERF]), lib.mlp_struct(fine, _NL[NET_NERF])
 
     @staticmethod
     def _forward_fused(ctx, batch, cfg, d, coarse, fine, same, need_grad):
@@ -565,8 +597,7 @@ class March(torch.autograd.Function):
         if Ni > 0:
             rgb0, depth0, acc0, density0, z_std = f(R, 3), f(R), f(R), f(R, S - 1), f(R)
             o.rgb0, o.depth0, o.acc0, o.density0, o.z_std = (t.data_ptr() for t in (rgb0, depth0, acc0, density0, z_std))
-        dr = lib.MarchDraws(*(None if d.get(k) is None else d[k].data_ptr() for k in ("t_rand", "noise_c", "u", "noise_f")))
-        stc, stf = lib.mlp_struct(coarse, _NL[NET_NERF]), lib.mlp_struct(fine, _NL[NET_NERF])
+        dr, stc, stf = March._c_args(d, coarse, fine)
         lib.call("lush_march_fwd", C.byref(c), lib.ptr(batch), C.byref(stc), C.byref(stf), C.byref(dr), C.byref(o), lib.ptr(ws),
                  lib.ptr(cfg.flags), _stream())
         outs = [rgb, depth, acc, density, March._view(ws, c, lib.VIEW_RAW, (R, Sl, 4)), March._view(ws, c, lib.VIEW_WEIGHTS, (R, Sl)),
@@ -574,11 +605,8 @@ class March(torch.autograd.Function):
         if Ni > 0:
             outs += [rgb0, depth0, acc0, density0, z_std]
         if cfg.hooks.keep is not None and need_grad:
-            def raw_view(which):
-                off, nb = C.c_size_t(), C.c_size_t()
-                lib.call("lush_march_view", C.byref(c), which, C.byref(off), C.byref(nb))
-                return ws[off.value:off.value + nb.value]
-            cfg.hooks.keep.update(stash_c=raw_view(lib.VIEW_STASH_COARSE), stash_f=raw_view(lib.VIEW_STASH_FINE) if Ni > 0 else None,
+            cfg.hooks.keep.update(stash_c=March._view_bytes(ws, c, lib.VIEW_STASH_COARSE),
+                                  stash_f=March._view_bytes(ws, c, lib.VIEW_STASH_FINE) if Ni > 0 else None,
                                   P_c=R * S, P_f=R * Sl if Ni > 0 else 0, batch=batch)
         ctx.fused = True
         return outs, [ws]
@@ -618,16 +646,13 @@ class March(torch.autograd.Function):
             buf_f, ret_f = grads_for(fine, ran_f)
         # (the first pass that runs writes d(ray batch) whole: no zero-fill launch; nothing runs when no output gradient arrived)
         drays = torch.empty_like(batch) if (ran_f or ran_c) else torch.zeros_like(batch)
-        dr = lib.MarchDraws(*(None if d.get(k) is None else d[k].data_ptr() for k in ("t_rand", "noise_c", "u", "noise_f")))
-        stc, stf = lib.mlp_struct(coarse, _NL[NET_NERF]), lib.mlp_struct(fine, _NL[NET_NERF])
+        dr, stc, stf = March._c_args(d, coarse, fine)
         gc = lib.mlp_struct(buf_c, _NL[NET_NERF]) if buf_c is not None else None
         gf = lib.mlp_struct(buf_f, _NL[NET_NERF]) if buf_f is not None else None
         lib.call("lush_march_bwd", C.byref(c), lib.ptr(batch), C.byref(stc), C.byref(stf), C.byref(dr), C.byref(go), lib.ptr(ws),
                  None if gc is None else C.byref(gc), None if gf is None else C.byref(gf), lib.ptr(drays), _stream())
         if cfg.hooks.live_acc is not None and (ran_f or ran_c) and not (c.variant & lib.VARIANT_DENSE_BWD) and live_backward(cfg.precision, None):
-            off, nb = C.c_size_t(), C.c_size_t()
-            lib.call("lush_march_view", C.byref(c), lib.VIEW_LIVE_COUNTS, C.byref(off), C.byref(nb))
-            cnt = ws[off.value:off.value + 16].view(torch.int32)
+            cnt = March._view_bytes(ws, c, lib.VIEW_LIVE_COUNTS).view(torch.int32)      # 16 bytes: {live, all} of the fine and the coarse pass
             if not (ran_f and ran_c) or not fine_on:      # a pass that did not run left its slot untouched
                 cnt = cnt.clone()
                 if not fine_on or not ran_c:
@@ -652,41 +677,38 @@ class March(torch.autograd.Function):
         c = March._c_cfg(cfg, batch.shape[0], same, need_grad)
         trunk = live and bool(lib.load().lush_march_trunk_form(C.byref(c)))
         trunk_c = trunk and March._ask_coarse_trunk(c)
-        ctx.trunk, ctx.trunk_c = trunk, trunk_c
-        fwd_list = []
 
         def fwd_pass(tensors, pk, z, final, noise):
             if not (trunk if final else trunk_c):
-                return mlp_forward(NET_NERF, pf, tensors, pk, batch, z, stash_fwd, stash_code(pf, pb), var, tm, grp)
+                raw, stash = mlp_forward(NET_NERF, pf, tensors, pk, batch, z, stash_fwd, stash_code(pf, pb), var, tm, grp)
+                return _PiecePass(z, raw, stash if stash is not None else torch.empty(0, device=batch.device))
             raw = mlp_forward_trunk(pf, pk, batch, z, var, tm, grp)
             lidx, ray_start, cnt = live_list(raw, z, noise, cfg.raw_noise_std, cfg.near_mask)
-            fwd_list.extend((lidx, ray_start, cnt))      # (the coarse pass's first when both passes list)
-            return raw, mlp_forward_live(NET_NERF, pf, tensors, pk, batch, z, lidx, cnt, stash_code(pf, pb), var, tm, raw=raw)
+            stash = mlp_forward_live(NET_NERF, pf, tensors, pk, batch, z, lidx, cnt, stash_code(pf, pb), var, tm, raw=raw)
+            return _PiecePass(z, raw, stash, (lidx, ray_start, cnt))
         zc = zgrid(batch, cfg.N_samples, cfg.lindisp, d.get("t_rand"))
         pk_c = mlp_pack(NET_NERF, pf, coarse, var)
-        raw_c, stash_c = fwd_pass(coarse, pk_c, zc, cfg.N_importance == 0, d.get("noise_c"))
-        rgb, depth, acc, weights, density = composite_fwd(raw_c, zc, batch, d.get("noise_c"), cfg,
+        pc = fwd_pass(coarse, pk_c, zc, cfg.N_importance == 0, d.get("noise_c"))
+        rgb, depth, acc, weights, density = composite_fwd(pc.raw, zc, batch, d.get("noise_c"), cfg,
                                                           lib.FAULT_COARSE_SHIFT if cfg.N_importance > 0 else 0)
         outs = [rgb, depth, acc, density]
-        z_last, raw_last, w_last = zc, raw_c, weights
-        saved = [zc, raw_c, stash_c if stash_c is not None else torch.empty(0, device=batch.device)]
+        passes, w_last = [pc], weights
         if cfg.N_importance > 0:
             zf, _, z_std = sample_merge(zc, weights, cfg.N_importance, d.get("u"), cfg.flags)
             pk_f = pk_c if same else mlp_pack(NET_NERF, pf, fine, var)
-            raw_f, stash_f = fwd_pass(fine, pk_f, zf, True, d.get("noise_f"))
-            rgb1, depth1, acc1, weights1, density1 = composite_fwd(raw_f, zf, batch, d.get("noise_f"), cfg)
+            passes.append(fwd_pass(fine, pk_f, zf, True, d.get("noise_f")))
+            rgb1, depth1, acc1, w_last, density1 = composite_fwd(passes[1].raw, zf, batch, d.get("noise_f"), cfg)
             outs = [rgb1, depth1, acc1, density1]
-            saved += [zf, raw_f, stash_f if stash_f is not None else torch.empty(0, device=batch.device)]
-            z_last, raw_last, w_last = zf, raw_f, weights1
-        R = batch.shape[0]
-        outs += [raw_last.view(R, -1, 4), w_last, z_last]
+        last = passes[-1]
+        outs += [last.raw.view(batch.shape[0], -1, 4), w_last, last.z]
         if cfg.N_importance > 0:
             outs += [rgb, depth, acc, density, z_std]
         if cfg.hooks.keep is not None:
-            cfg.hooks.keep.update(stash_c=saved[2], stash_f=saved[5] if cfg.N_importance > 0 else None, P_c=zc.numel(),
-                                  P_f=saved[3].numel() if cfg.N_importance > 0 else 0, batch=batch)
+            cfg.hooks.keep.update(stash_c=pc.stash, stash_f=last.stash if cfg.N_importance > 0 else None, P_c=zc.numel(),
+                                  P_f=last.z.numel() if cfg.N_importance > 0 else 0, batch=batch)
         ctx.fused = False
-        return outs, saved + fwd_list      # (trunk form: a pass's list, per-ray ranges and length, behind the passes' tensors)
+        ctx.has_list = [p.fwd_list is not None for p in passes]
+        return outs, _PiecePass.flatten(passes)
 
     @staticmethod
     def _backward_piecewise(ctx, g, batch, saved, d, coarse, fine):
@@ -700,17 +722,16 @@ class March(torch.autograd.Function):
         grads_f: List[Optional[torch.Tensor]] = []
 
         # trunk form: the final pass (the first to run here) has its list and its stash from the forward; in the coarse trunk form
-        # the coarse pass ahead of it has, too (saved in front of the final pass's)
-        fwd_list_final = saved[-3:] if getattr(ctx, "trunk", False) else None
-        fwd_list_coarse = saved[-6:-3] if getattr(ctx, "trunk_c", False) else None
+        # the coarse pass ahead of it has, too
+        passes = _PiecePass.rebuild(saved, ctx.has_list)
 
-        def run(tensors, z, raw, noise, stash, gg, final=False):
-            fwd_list = fwd_list_final if final else fwd_list_coarse
+        def run(tensors, p, noise, gg):
+            z, raw, stash = p.z, p.raw, p.stash
             draw = composite_bwd(raw, z, batch, noise, cfg, gg[0], gg[1], gg[2], drays)
             pk = mlp_pack(NET_NERF, pb, tensors, cfg.precision.variant)
-            if getattr(ctx, "live", False):      # (the one-call march does the same inside lush_march_bwd)
-                if fwd_list is not None:
-                    lidx, ray_start, cnt = fwd_list
+            if ctx.live:      # (the one-call march does the same inside lush_march_bwd)
+                if p.fwd_list is not None:
+                    lidx, ray_start, cnt = p.fwd_list
                     draw_c, _ = live_gather(draw, z.shape[0], z.shape[1], lidx, cnt)
                     st_live = stash
                 else:
@@ -727,9 +748,9 @@ class March(torch.autograd.Function):
             return gr
 
         if fine_on and any(x is not None for x in g_main):
-            grads_f = run(fine, saved[3], saved[4], d.get("noise_f"), saved[5], g_main, final=True)
+            grads_f = run(fine, passes[1], d.get("noise_f"), g_main)
         if any(x is not None for x in g_c):
-            grads_c = run(coarse, saved[0], saved[1], d.get("noise_c"), saved[2], g_c, final=not fine_on)
+            grads_c = run(coarse, passes[0], d.get("noise_c"), g_c)
         if fine_on and ctx.same and grads_f:
             grads_c = [(a + b if b is not None else a) if a is not None else b for a, b in zip(grads_c, grads_f)]
             grads_f = []

@@ -796,3 +796,51 @@ def test_weight_gradient_launch_plan_is_pinned():
     o = (ctypes.c_longlong * 80)()
     assert l.lush_debug_dw_plan(0, 3, 3, 4096, 0, 0, 256, o) != 0 and b"three planes" in l.lush_last_error()      # one launch per layer: no plan
     assert l.lush_debug_dw_plan(0, 17, 17, 1 << 27, 0, 0, 256, o) != 0 and l.lush_debug_dw_plan(0, 17, 17, 4096, 0, 0, 0, o) != 0
+
+
+MARCH_VIEWS = ("VIEW_Z", "VIEW_RAW", "VIEW_WEIGHTS", "VIEW_Z_COARSE", "VIEW_STASH_COARSE", "VIEW_STASH_FINE", "VIEW_LIVE_COUNTS")
+
+
+def march_layout_rows():
+    """{case key: [workspace bytes, trunk form, coarse trunk form, then (return code, offset, bytes) of each of MARCH_VIEWS]} over
+    the grid of test_march_layout_is_pinned, from the loaded library (a view that is refused reads (code, 0, 0))."""
+    import itertools
+    l, h = lib.load(), lib.PLANES_F16
+    shapes = ((7, 64, 64), (523, 44, 44), (20480, 64, 64), (4096, 64, 0), (1 << 20, 64, 64))
+    planes = ((h, h), (2, h), (2, 2), (3, 3), (h, 0))
+    variants = (0, lib.VARIANT_DENSE_BWD, lib.VARIANT_FWD_HALF, lib.VARIANT_PE_ROWS)
+    extras = (0, lib.MARCH_FWD_LIST_KEPT, lib.MARCH_COARSE_TRUNK, lib.MARCH_FWD_LIST_KEPT | lib.MARCH_COARSE_TRUNK)
+    rows = {}
+    for (R, S, ni), (pf, pb), var, extra, same in itertools.product(shapes, planes, variants, extras, (0, 1)):
+        c = lib.MarchCfgC(R, S, ni, 1.0, 1.0, 0, 0, -1.0, pf, pb, var | extra, same)      # (the other fields: tests/test_coarse_trunk._cfg)
+        row = [int(l.lush_march_workspace_bytes(ctypes.byref(c))), int(l.lush_march_trunk_form(ctypes.byref(c))),
+               int(l.lush_march_coarse_trunk_form(ctypes.byref(c)))]
+        for which in MARCH_VIEWS:
+            off, nb = ctypes.c_size_t(0), ctypes.c_size_t(0)
+            rc = int(l.lush_march_view(ctypes.byref(c), getattr(lib, which), ctypes.byref(off), ctypes.byref(nb)))
+            row += [rc, off.value, nb.value] if rc == 0 else [rc, 0, 0]
+        rows[f"{R},{S},{ni},{pf},{pb},{var},{extra},{same}"] = row
+    return rows
+
+
+def test_march_layout_is_pinned():
+    """Where every region of the march's workspace lies (layout() in lush_march_abi.hip), as far as the library tells without a
+    device: lush_march_workspace_bytes, the two form predicates and all seven lush_march_view answers, over shapes x plane codes x
+    kernel variants x the two bits of the word that are no kernel bits x one net or two.  Every row equals
+    tests/march_layout_expected.json, recorded with march_layout_rows() above from a library built from the sources as they stood
+    before layout() was rewritten around one record per pass -- not from the code under test.  The file holds each distinct row once
+    ("rows") and, per case, its number ("cases")."""
+    import json
+    want = json.load(open(os.path.join(ROOT, "tests", "march_layout_expected.json")))
+    got = march_layout_rows()
+    assert len(got) == len(want["cases"]) == 800 and list(got) == list(want["cases"])
+    for key, row in got.items():
+        assert row == want["rows"][want["cases"][key]], (key, row, want["rows"][want["cases"][key]])
+    # the grid reaches every form: the 2^27-point shape is refused everywhere (no bytes, no form, no view), the trunk form, the
+    # coarse trunk form, the live-point marches (the ones with a LIVE_COUNTS view)
+    rows = list(got.values())
+    refused = [r for r in rows if r[0] == 0]
+    assert len(refused) == 160 and all(r[1] == r[2] == 0 and all(r[3 + 3 * k] != 0 for k in range(7)) for r in refused)
+    assert sum(r[1] for r in rows) == 32 and sum(r[2] for r in rows) == 12
+    assert sum(1 for r in rows if r[0] and r[3 + 3 * MARCH_VIEWS.index("VIEW_LIVE_COUNTS")] == 0) == 96
+    assert len({tuple(r) for r in rows}) == len(want["rows"]) == 63

@@ -401,3 +401,68 @@ def test_piecewise_path_runs_the_same_form(diag):
     assert groups["mlp_fwd"]["launches"] == 2 and 0 < live < P_c + P_f
     # the backward's launches run on the lists the live forwards ran on: the fine pass's is the forward's own
     assert groups["mlp_bwd_chain"]["points"] == live and groups["mlp_bwd_weights"]["points"] == live
+
+
+_CROSS_INPUTS = {}
+
+
+def _cross_inputs():
+    """7 rays x (64 + 64) samples on the default-init field, noise and perturb on: (coarse tensors, fine tensors, ray batch, draws,
+    upstream gradients of rgb, depth, acc, rgb0, depth0, acc0).  Made once per session; nobody writes to them."""
+    if not _CROSS_INPUTS:
+        from lush_nerf_amd import ops, synth
+        dev = torch.device("cuda:0")
+        R, S, Ni, seed = 7, 64, 64, 3
+        w = synth.all_weights(30, seed)
+        names = lambda net: [k.replace("mlp_fine", net) for k in NAMES]
+        rays = torch.from_numpy(synth.ray_batch(R, seed, 30)["rays"]).to(dev)
+        g = torch.Generator().manual_seed(9)
+        _CROSS_INPUTS.update(
+            coarse=[torch.from_numpy(w[k].copy()).to(dev) for k in names("mlp_coarse")],
+            fine=[torch.from_numpy(w[k].copy()).to(dev) for k in names("mlp_fine")],
+            batch=ops.PackRays.apply(rays, synth.H_DEF, synth.W_DEF, synth.FOCAL_DEF, True, 0., 1.).detach(),
+            draws={k: torch.from_numpy(v).to(dev) for k, v in synth.draws(R, S, Ni, seed).items()},
+            up=[torch.randn(*s, generator=g).to(dev) for s in ((R, 3), (R,), (R,), (R, 3), (R,), (R,))])
+    return _CROSS_INPUTS
+
+
+@pytest.mark.gpu
+@pytest.mark.parametrize("into", ["both", "main", "coarse"])
+@pytest.mark.parametrize("nets", [1, 2])
+@pytest.mark.parametrize("planes", ["h,h", "2,h"])
+def test_one_call_march_equals_the_piecewise_path_across_forms(diag, planes, nets, into):
+    """The one-call march (lush_march_fwd / lush_march_bwd) against the piecewise path, which composes the same kernels on its own
+    in ops.March: the backward's fragments of the forward's plane code or of another one (2,h: packed for the backward), one net
+    for both passes or two, and output gradients into both passes, the final pass alone or the coarse pass alone.  Outputs bit for
+    bit, gradients to the form-against-form gates, and the net of a pass that received no gradient gets None from both.  Written
+    against the library as it stood before lush_march_abi.hip was laid out per pass, where all twelve cases passed with the figures
+    they have since: identical gradients except with one net and gradients into both passes (L2 4e-08, worst tensor 2e-07)."""
+    from lush_nerf_amd import ops
+    x = _cross_inputs()
+    prec = ops.Precision(*ops.parse_planes(planes))
+    main, coarse_out = (0, 1, 2), (7, 8, 9)
+    used = {"both": main + coarse_out, "main": main, "coarse": coarse_out}[into]
+
+    def run(timer):
+        coarse = [t.clone().requires_grad_(True) for t in x["coarse"]]
+        fine = [t.clone().requires_grad_(True) for t in x["fine"]] if nets == 2 else []
+        batch = x["batch"].clone().requires_grad_(True)
+        cfg = ops.MarchCfg(64, 64, 1., 1., precision=prec, want_grad=True, hooks=ops.Hooks(timer=ops.KernelTimer() if timer else None))
+        out = ops.March.apply(batch, cfg, x["draws"], len(coarse), *coarse, *fine)
+        up = dict(zip(main + coarse_out, x["up"]))
+        sum((out[i] * up[i]).sum() for i in used).backward()
+        torch.cuda.synchronize()
+        grads = {**{f"c{i}": t.grad for i, t in enumerate(coarse)}, **{f"f{i}": t.grad for i, t in enumerate(fine)}, "d rays": batch.grad}
+        return [o.detach().clone() for o in out], grads
+    out_f, g_f = run(False)
+    out_p, g_p = run(True)
+    assert len(out_f) == len(out_p) == 12
+    for k, (a, b) in enumerate(zip(out_f, out_p)):
+        assert torch.isfinite(a).all() and torch.equal(a, b), k
+    # which nets received gradients: with one net every case reaches it; with two, only the pass whose outputs were used
+    for g in (g_f, g_p):
+        assert g["d rays"] is not None and all(float(t.abs().max()) > 0 for t in g.values() if t is not None)
+        assert all((g[f"c{i}"] is None) == (nets == 2 and into == "main") for i in range(len(NAMES)))
+        assert nets == 1 or all((g[f"f{i}"] is None) == (into == "coarse") for i in range(len(NAMES)))
+    _grads_agree("cross", g_f, g_p, f"one-call march against the piecewise path [{planes}, {nets} net(s), gradients into {into}]")
+    _grads_agree("cross", g_p, g_f, f"piecewise path against the one-call march [{planes}, {nets} net(s), gradients into {into}]")
