@@ -18,6 +18,8 @@ blur kernel is on; [mlp_noise_coarse.alpha_linear] never.
 """
 from __future__ import annotations
 
+from contextlib import contextmanager
+from dataclasses import dataclass, field
 from typing import Dict, List, Optional
 
 import torch
@@ -103,6 +105,139 @@ def adam_segments(model: NeRFAll) -> List[List[torch.nn.Parameter]]:
     return [base, late, dead]
 
 
+class LivePolicy:
+    """Which backward a step runs, the live-point one or the one over all the points (include/lush_march.h "Live points"): the share
+    of MLP evaluation points whose d_raw row is non-zero, counted on the device by every live-point march and followed on the host
+    through snapshots in pinned memory.  Owns the mode, the thresholds, where the choice stands, the device accumulator, the pinned
+    ring, the snapshots in flight and the previous readings.  Needs no GPU: `device` may be the CPU, and `event` any type with
+    record() / synchronize() (the CPU tests)."""
+
+    # The live-point march costs one forward over all the points more than the dense one and saves (1 - share) of the stash-
+    # writing forward, the chain and the weight gradients: measured on BASELINE config 2 over 420 - 600 training steps
+    # (profiles/r05_live_points.md), 4.4 .. 5.3 + 14.5 .. 17.4 x share ms against 16.1 .. 16.7 ms: break-even at a share of
+    # 0.69 .. 0.76.  Above MAX_SHARE the trainer runs the dense backward and looks again (one live step, which at such a
+    # share costs what a dense one does) every PROBE_EVERY steps; it returns to the live march below MIN_SHARE.
+    # (Round 5 switched at 0.65 / 0.60 and probed every 32 steps: inside the band where the live march is still the cheaper one,
+    # and up to 32 steps late on a falling share.)
+    MAX_SHARE, MIN_SHARE, PROBE_EVERY = 0.70, 0.65, 8
+    # The choice for step i is taken from the counts of step i - LAG, whatever the host's and the device's relative timing:
+    # choose() WAITS for that step's snapshot (two steps behind the one being enqueued: it has all but always arrived, and the
+    # host never gets more than LAG steps ahead of the device), so a run with a fixed seed makes the same choices every time
+    # (round 5 polled with event.query(): which steps ran dense depended on how far the host was ahead).
+    LAG = 2
+
+    def __init__(self, device, event=None):
+        device = torch.device(device)
+        self.mode = "auto"                # "auto": dense backward while the share stays above MAX_SHARE; "live" / "dense": always
+        self.share = None                 # share of live points in the most recent step whose counts have arrived
+        self.dense_now, self.dense_steps = False, 0
+        self.step = 0                     # steps whose backward choice has been taken
+        self.acc = torch.zeros(4, dtype=torch.int64, device=device)      # cumulative {live, all} of the fine and the coarse passes
+        ring = torch.zeros(8, 4, dtype=torch.int64)
+        self.ring = ring.pin_memory() if device.type == "cuda" else ring
+        self.in_flight = []               # [(event, ring row, step number, accumulator id)], oldest first
+        self._event = event or torch.cuda.Event
+        self._slot = 0
+        self._owed = False                # the step whose choice was taken last ran (or runs) the live march and has no snapshot yet
+        self._prev = {}                   # accumulator id -> last reading: of `acc`, and of the caller's accumulator read last
+
+    def choose(self) -> bool:
+        """The choice for the step that starts now (True: the dense backward): counts the step and consumes the snapshots of the
+        steps up to LAG behind it (a host wait: see LAG)."""
+        self.step += 1
+        own = self.acc.data_ptr()
+        while self.in_flight and self.in_flight[0][2] <= self.step - self.LAG:
+            ev, row, _, acc_id = self.in_flight.pop(0)
+            ev.synchronize()
+            cur = [int(x) for x in self.ring[row].tolist()]
+            prev = self._prev.get(acc_id, [0, 0, 0, 0])      # (an accumulator not read before: a series that starts at zero)
+            d_live = (cur[0] - prev[0]) + (cur[2] - prev[2])
+            d_all = (cur[1] - prev[1]) + (cur[3] - prev[3])
+            if d_all > 0:
+                self.share = d_live / d_all
+            # (bounded: a caller may hand in a fresh tensor every step; `acc` keeps its reading through any number of those)
+            self._prev = {k: v for k, v in self._prev.items() if k == own}
+            self._prev[acc_id] = cur
+        dense = self.decide()
+        self._owed = not dense
+        return dense
+
+    def decide(self) -> bool:
+        """The decision alone, from the share that has arrived."""
+        if self.mode == "dense":
+            return True
+        if self.mode == "live" or self.share is None:
+            return False
+        if self.dense_now:
+            self.dense_steps += 1
+            if self.dense_steps % self.PROBE_EVERY == 0:
+                return False                                   # one live step: look at the share again
+            if self.share < self.MIN_SHARE:
+                self.dense_now = False
+        elif self.share > self.MAX_SHARE:
+            self.dense_now, self.dense_steps = True, 0
+        return self.dense_now
+
+    def snapshot(self, acc=None) -> bool:
+        """Enqueue a copy of the cumulative counts the step's marches added to (`acc`, or the one a caller handed the march) into
+        the next row of the pinned ring, and an event behind it (no allocation, no wait).  Only for the step whose choice was
+        just taken and came out "live", once: anything else is not enqueued, so choose() leaves at most LAG + 1 in flight."""
+        if not self._owed:
+            return False
+        acc = self.acc if acc is None else acc
+        assert len(self.in_flight) <= self.LAG < self.ring.shape[0], (len(self.in_flight), self.LAG)
+        row = self._slot
+        self._slot = (row + 1) % self.ring.shape[0]
+        self.ring[row].copy_(acc, non_blocking=True)
+        ev = self._event()
+        ev.record()
+        self.in_flight.append((ev, row, self.step, acc.data_ptr()))
+        self._owed = False
+        return True
+
+    def counts(self):
+        """Cumulative {live, all} point counts of the fine and the coarse passes in `acc` (a synchronisation)."""
+        return [int(x) for x in self.acc.tolist()]
+
+    def state(self) -> dict:
+        """Where the policy stands (checkpoint.save_checkpoint keeps it; the advisor's note of round 5: none of it was part of any
+        saved state).  The snapshots still in flight belong to steps the file does not contain and are dropped on load."""
+        return {"policy": self.mode, "dense_now": bool(self.dense_now), "dense_steps": int(self.dense_steps),
+                "live_share": None if self.share is None else float(self.share)}
+
+    def load_state(self, st: Optional[dict]):
+        """(`policy` in the file is a record of how the saved run was set up; the resuming caller's own mode stays)"""
+        self.in_flight, self.step, self._owed = [], 0, False
+        self._prev = {self.acc.data_ptr(): self.counts()}
+        st = st or {"dense_now": False, "dense_steps": 0, "live_share": None}
+        self.dense_now, self.dense_steps, self.share = bool(st["dense_now"]), int(st["dense_steps"]), st["live_share"]
+
+
+@dataclass
+class _CapturedStep:
+    """One backward choice of the captured step: [zero grad, forward, backward, Adam, state advance] in g1, or the last two in g2."""
+    g1: torch.cuda.CUDAGraph
+    g2: Optional[torch.cuda.CUDAGraph]
+    loss: torch.Tensor
+    calls: int                            # lush_draws calls of one step
+    mask: int                             # Adam segments the step moves
+    acc: torch.Tensor                     # the accumulator its marches add their live counts to
+
+
+@dataclass
+class _Capture:
+    """Trainer.step_graph's captured step: what its choices share, and one _CapturedStep per backward choice."""
+    key: Optional[tuple]
+    static: dict                          # the graphs' own copy of the batch
+    state: torch.Tensor                   # the device step state ...
+    mirror: tuple                         # ... and the host's record of what it holds
+    pool: Optional[tuple] = None
+    sub: Dict[Optional[bool], _CapturedStep] = field(default_factory=dict)
+
+
+_ASK = object()      # Trainer.step(_dense=_ASK): take the backward choice here (None: the policy is not consulted for this step)
+
+
 class Trainer:
     def __init__(self, model: NeRFAll, H: int, W: int, focal: float, N_samples: int = 64, N_importance: int = 64,
                  lrate: float = 5e-4, lrate_decay: int = 250, perturb: float = 1., raw_noise_std: float = 1.,
@@ -143,23 +278,11 @@ class Trainer:
         self.allreduce_events = None      # set to a list to collect (start, end) HIP events of every step's all-reduce
         # scratch of the loss kernel's reduction (zero once, left zero by every launch: no zero-fill per step)
         self._loss_work = torch.zeros(2, dtype=torch.float32, device=self.flat.param.device) if self.flat.param.is_cuda else None
-        # live-point backward (include/lush_march.h "Live points"): the share of MLP evaluation points whose d_raw row is non-zero,
-        # counted on the device by every march and followed on the host WITHOUT blocking (snapshots through pinned memory)
-        self.live_policy = "auto"         # "auto": dense backward while the share stays above LIVE_MAX_SHARE; "live" / "dense": always
-        self._live_cum = torch.zeros(4, dtype=torch.int64, device=self.flat.param.device) if self.flat.param.is_cuda else None
-        self._live_ring = torch.zeros(8, 4, dtype=torch.int64).pin_memory() if self.flat.param.is_cuda else None
-        self._live_slot = 0
-        self._live_snaps = []             # [(event, ring row, step number, accumulator id)], oldest first
-        self._live_prev = [0, 0, 0, 0]    # last snapshot read (cumulative counts)
-        self._live_prev_acc = None        # ... and the accumulator it was read from (a caller may hand the march its own)
-        self._live_step = 0               # steps whose backward choice has been taken
-        self.live_share = None            # share of live points in the most recent step whose counts have arrived
-        self._dense_now = False
-        self._dense_steps = 0
-        self._eager_seen = set()          # backward choices (dense: bool) that have run as an eager step (step_graph captures only those)
+        self.live = LivePolicy(self.flat.param.device)      # live-point or dense backward, per step (consulted on the GPU only)
+        self._eager_seen = set()          # backward choices (dense: True / False, None: policy not consulted) that have run as an eager step
         self._pack_plan = None            # ops.PackPlan of the model's networks in the current precision mode
         self._pack_plans = {}             # ... by signature (precision mode, kernel variant, parameter addresses)
-        self._graph = None                # step_graph: the captured step (graphs, static batch / loss, device step state + host mirror)
+        self._graph = None                # step_graph: the captured step (_Capture)
         self._graph_eager_left = 2        # plain steps before the capture (every lazy initialisation behind the entry points has run)
         self.sync_replicas()
 
@@ -195,6 +318,23 @@ class Trainer:
         g = max(self.global_step - 1, 0)
         return self.lrate * (0.1 ** (g / (self.lrate_decay * 1000)))
 
+    # ------------------------------------------------------------------ the live-point policy's public names
+    live_policy = property(lambda self: self.live.mode, lambda self, v: setattr(self.live, "mode", v))
+    live_share = property(lambda self: self.live.share, lambda self, v: setattr(self.live, "share", v))
+    _dense_now = property(lambda self: self.live.dense_now)           # (bench.py reads these two)
+    _dense_steps = property(lambda self: self.live.dense_steps)
+
+    def live_counts(self):
+        """Cumulative {live, all} point counts of the fine and the coarse passes of every live-point march so far (a
+        synchronisation; bench.py reads it around its timed region)."""
+        return self.live.counts()
+
+    def live_policy_state(self) -> dict:
+        return self.live.state()
+
+    def load_live_policy_state(self, st: Optional[dict]):
+        self.live.load_state(st)
+
     # ------------------------------------------------------------------ small launches: 128-point tiles
     # A march whose largest MLP launch has at most this many points runs on the 128-point-tile kernels (two workgroups per CU:
     # lib.VARIANT_FWD_HALF | VARIANT_BWD_HALF) instead of the 256-point-tile ones: BASELINE config 1's 8 192 points are 32 of
@@ -203,135 +343,46 @@ class Trainer:
     # 77 / 80 / 118 -> 74 / 69 / 115; R = 2 048: 92 / 96 / 189 -> 110 / 109 / 160 (the big tiles win from there).
     SMALL_LAUNCH_POINTS = 32768
 
-    # The live-point march costs one forward over all the points more than the dense one and saves (1 - share) of the stash-
-    # writing forward, the chain and the weight gradients: measured on BASELINE config 2 over 420 - 600 training steps
-    # (profiles/r05_live_points.md), 4.4 .. 5.3 + 14.5 .. 17.4 x share ms against 16.1 .. 16.7 ms: break-even at a share of
-    # 0.69 .. 0.76.  Above LIVE_MAX_SHARE the trainer runs the dense backward and looks again (one live step, which at such a
-    # share costs what a dense one does) every LIVE_PROBE_EVERY steps; it returns to the live march below LIVE_MIN_SHARE.
-    # (Round 5 switched at 0.65 / 0.60 and probed every 32 steps: inside the band where the live march is still the cheaper one,
-    # and up to 32 steps late on a falling share.)
-    LIVE_MAX_SHARE, LIVE_MIN_SHARE, LIVE_PROBE_EVERY = 0.70, 0.65, 8
-    # The choice for step i is taken from the counts of step i - LIVE_LAG, whatever the host's and the device's relative timing:
-    # the trainer WAITS for that step's snapshot (two steps behind the one being enqueued: it has all but always arrived, and the
-    # host never gets more than LIVE_LAG steps ahead of the device), so a run with a fixed seed makes the same choices every time
-    # (round 5 polled with event.query(): which steps ran dense depended on how far the host was ahead).
-    LIVE_LAG = 2
-
-    def _live_poll(self):
-        """Consume the count snapshots of the steps up to LIVE_LAG behind the one that starts now (waits for them: see LIVE_LAG):
-        updates live_share."""
-        while self._live_snaps and self._live_snaps[0][2] <= self._live_step - self.LIVE_LAG:
-            ev, row, _, acc_id = self._live_snaps.pop(0)
-            ev.synchronize()
-            cur = [int(x) for x in self._live_ring[row].tolist()]
-            if acc_id != self._live_prev_acc:          # another accumulator (a caller's own, e.g. one per step): a series that starts at zero
-                self._live_prev, self._live_prev_acc = [0, 0, 0, 0], acc_id
-            d_live = (cur[0] - self._live_prev[0]) + (cur[2] - self._live_prev[2])
-            d_all = (cur[1] - self._live_prev[1]) + (cur[3] - self._live_prev[3])
-            if d_all > 0:
-                self.live_share = d_live / d_all
-            self._live_prev = cur
-
-    def _live_snapshot(self, acc=None):
-        """Enqueue a copy of the cumulative counts the step's marches added to (the trainer's accumulator, or the one a caller put
-        into hooks.live_acc) into the next row of the pinned ring (no allocation, nothing blocks)."""
-        acc = self._live_cum if acc is None else acc
-        if acc is None or self._live_ring is None or len(self._live_snaps) >= self._live_ring.shape[0]:
-            return                         # (cannot happen with LIVE_LAG < ring rows; a skipped step's delta folds into the next snapshot)
-        row = self._live_slot
-        self._live_slot = (row + 1) % self._live_ring.shape[0]
-        self._live_ring[row].copy_(acc, non_blocking=True)
-        ev = torch.cuda.Event()
-        ev.record()
-        if self._live_prev_acc is None:
-            self._live_prev_acc = acc.data_ptr()       # (the first series starts from zero counts)
-        self._live_snaps.append((ev, row, self._live_step, acc.data_ptr()))
-
-    def live_counts(self):
-        """Cumulative {live, all} point counts of the fine and the coarse passes of every live-point march so far (a
-        synchronisation; bench.py reads it around its timed region)."""
-        return [0, 0, 0, 0] if self._live_cum is None else [int(x) for x in self._live_cum.tolist()]
-
-    def live_policy_state(self) -> dict:
-        """Where the policy stands (checkpoint.save_checkpoint keeps it; the advisor's note of round 5: none of it was part of any
-        saved state).  The snapshots still in flight belong to steps the file does not contain and are dropped on load."""
-        return {"policy": self.live_policy, "dense_now": bool(self._dense_now), "dense_steps": int(self._dense_steps),
-                "live_share": None if self.live_share is None else float(self.live_share)}
-
-    def load_live_policy_state(self, st: Optional[dict]):
-        self._live_snaps, self._live_step = [], 0
-        if self._live_cum is not None:
-            self._live_prev, self._live_prev_acc = [int(x) for x in self._live_cum.tolist()], self._live_cum.data_ptr()
-        if st is None:
-            self._dense_now, self._dense_steps, self.live_share = False, 0, None
-            return
-        # (`policy` in the file is a record of how the saved run was set up; the resuming caller's own live_policy stays)
-        self._dense_now, self._dense_steps, self.live_share = bool(st["dense_now"]), int(st["dense_steps"]), st["live_share"]
-
-    def _dense_backward_now(self) -> bool:
-        """The policy's choice for the step that starts now."""
-        if self.live_policy == "dense":
-            return True
-        if self.live_policy == "live" or self.live_share is None:
-            return False
-        if self._dense_now:
-            self._dense_steps += 1
-            if self._dense_steps % self.LIVE_PROBE_EVERY == 0:
-                return False                                   # one live step: look at the share again
-            if self.live_share < self.LIVE_MIN_SHARE:
-                self._dense_now = False
-        elif self.live_share > self.LIVE_MAX_SHARE:
-            self._dense_now, self._dense_steps = True, 0
-        return self._dense_now
-
-    def _largest_launch(self, n_rays: int, force_naive: bool, coarse_only: bool = False) -> int:
+    def _step_form(self, n_rays: int, force_naive: bool, coarse_only: bool = False):
+        """(the precision mode a step on n_rays rays per march runs in before the backward choice, whether the live-point policy
+        is consulted for it): the model's mode and "yes, if that mode runs the live-point backward with no explicit kernel
+        variant" -- except that the headline mode runs a step whose largest MLP launch is small on the small-launch kernel
+        variant, which has no live-point form."""
+        pr = self.model.precision
         M = 1 if (force_naive or coarse_only or self.model.blur_kernel_net is None) else self.model.mlp_rbk.num_motion + 1
-        Ni = 0 if coarse_only else int(self.kw["N_importance"])
-        return int(n_rays) * M * (int(self.kw["N_samples"]) + Ni)
+        points = int(n_rays) * M * (int(self.kw["N_samples"]) + (0 if coarse_only else int(self.kw["N_importance"])))
+        if pr.variant == 0 and pr.fwd == ops.PLANES_F16 and pr.bwd == ops.PLANES_F16 and points <= self.SMALL_LAUNCH_POINTS:
+            return ops.Precision(pr.fwd, pr.bwd, ops.lib.VARIANT_FWD_HALF | ops.lib.VARIANT_BWD_HALF), False
+        return pr, pr.variant == 0 and ops.live_backward(pr, None) and self.flat.param.is_cuda and not coarse_only
 
-    def _headline_default(self) -> bool:
-        pr = self.model.precision
-        return pr.variant == 0 and pr.fwd == ops.PLANES_F16 and pr.bwd == ops.PLANES_F16
+    def _backward_choice(self, n_rays: int, force_naive: bool) -> Optional[bool]:
+        """True: the step that starts now runs the dense backward; None: the policy has no say in this step.  Decided on the host
+        from the counts that have arrived, OUTSIDE any graph capture (step_graph keeps one captured step per answer)."""
+        return self.live.choose() if self._step_form(n_rays, force_naive)[1] else None
 
-    def _live_mode(self) -> bool:
-        """The model's precision mode runs the live-point backward (and no explicit kernel variant is set)."""
-        pr = self.model.precision
-        return pr.variant == 0 and ops.live_backward(pr, None)
+    def _step_precision(self, n_rays: int, force_naive: bool, dense: Optional[bool] = None, coarse_only: bool = False):
+        """The precision mode this step's kernels run in: _step_form's, with the dense backward when _backward_choice said so."""
+        pr, consulted = self._step_form(n_rays, force_naive, coarse_only)
+        return ops.Precision(pr.fwd, pr.bwd, ops.lib.VARIANT_DENSE_BWD) if dense and consulted else pr
 
-    def _backward_choice(self, n_rays: int, force_naive: bool) -> bool:
-        """True: the step that starts now runs the dense backward.  Decided on the host from the counts that have arrived, OUTSIDE
-        any graph capture (step_graph keeps one captured step per answer)."""
-        if not self._live_mode() or self._live_cum is None:
-            return False
-        if self._headline_default() and self._largest_launch(n_rays, force_naive) <= self.SMALL_LAUNCH_POINTS:
-            return False                                       # (the small-launch kernels: no live-point form)
-        self._live_step += 1
-        self._live_poll()
-        return self._dense_backward_now()
-
-    def _step_precision(self, n_rays: int, force_naive: bool, coarse_only: bool = False, dense: bool = False):
-        """The precision mode this step's kernels run in: the model's, with the small-launch kernel variant when the step's
-        largest MLP launch is small (headline mode only), or with the dense backward when _backward_choice said so (an explicit
-        variant is left alone)."""
-        pr = self.model.precision
-        if self._headline_default() and self._largest_launch(n_rays, force_naive, coarse_only) <= self.SMALL_LAUNCH_POINTS:
-            return ops.Precision(pr.fwd, pr.bwd, ops.lib.VARIANT_FWD_HALF | ops.lib.VARIANT_BWD_HALF)
-        if dense and self._live_mode():
-            return ops.Precision(pr.fwd, pr.bwd, ops.lib.VARIANT_DENSE_BWD)
-        return pr
-
-    class _PrecisionFor:
-        """with self._PrecisionFor(model, precision): the model's ops run in `precision` (packing and every launch of the step
-        must agree on the kernel variant: the stash formats differ)."""
-
-        def __init__(self, model, precision):
-            self.model, self.precision = model, precision
-
-        def __enter__(self):
-            self.saved, self.model.precision = self.model.precision, self.precision
-
-        def __exit__(self, *a):
-            self.model.precision = self.saved
+    @contextmanager
+    def _stepping(self, precision, **fields):
+        """with self._stepping(precision, state=..., live_acc=...): the model's ops run in `precision` (packing and every launch of
+        the step must agree on the kernel variant: the stash formats differ), the dW kernels add straight into the flat gradient
+        (hooks.sink; p.grad are views of it) and the hook fields named hold the values given.  On exit the precision, the sink
+        and exactly those fields are what they were, and the step's packed weights are dropped."""
+        model, hooks = self.model, self.model.hooks
+        fields["sink"] = True
+        saved_precision, saved = model.precision, {k: getattr(hooks, k) for k in fields}
+        model.precision = precision
+        for k, v in fields.items():
+            setattr(hooks, k, v)
+        try:
+            yield
+        finally:
+            model.precision, hooks.packed = saved_precision, None
+            for k, v in saved.items():
+                setattr(hooks, k, v)
 
     # ------------------------------------------------------------------ weights packed once per step
     def _pack_entries(self):
@@ -400,57 +451,82 @@ class Trainer:
             (loss_rgb * weight).backward()
         return loss_rgb.detach()
 
-    def step(self, batch: Dict[str, torch.Tensor], i: int, draws=None, consist: Optional[dict] = None, _dense: Optional[bool] = None):
-        """One optimisation step on a batch {rays [N,3,2] (or c2w/view/px/py for device-side ray generation),
-        images_idx [N,1], target [N,3], fq_mask [N]}."""
-        self.model.train()
-        force_naive = i < self.kernel_start_iter
+    # ------------------------------------------------------------------ the two halves of every step
+    def _micro(self, N: int) -> int:
+        """Rays per forward + backward (and so per march) of a step on N rays."""
+        return self.micro_batch if 0 < self.micro_batch < N else N
+
+    def _grads(self, batch, i, force_naive, draws=None):
+        """The gradients of a step, inside _stepping: ONE launch zeroes the flat gradient and packs the weights, then forward +
+        backward of every micro-batch, with the explicit draws or (hooks.state set) the device step state's Philox counter."""
         N = batch["target"].shape[0]
-        mb = self.micro_batch if 0 < self.micro_batch < N else N
-        dense = self._backward_choice(mb, force_naive) if _dense is None else _dense
-        self._eager_seen.add(dense)
+        mb = self._micro(N)
+        self._pack_weights(zero_grad=True)
         loss = None
-        hooks = self.model.hooks
-        sink_before, hooks.sink = hooks.sink, True
-        acc_before = hooks.live_acc
-        if hooks.live_acc is None:
-            hooks.live_acc = self._live_cum
-        try:      # dW kernels add straight into the flat gradient (p.grad are views of it)
-            step_prec = self._step_precision(mb, force_naive, dense=dense)
-            with self._PrecisionFor(self.model, step_prec):
-                self._pack_weights(zero_grad=True)
-                for a in range(0, N, mb):
-                    b = min(a + mb, N)
-                    part = self._fwd_bwd(batch, a, b, i, draws, (b - a) / N, force_naive)
-                    loss = part if loss is None else loss + part
-            if consist is not None and i >= self.noisenerf_start_iter:
-                # computed from i >= noisenerf_start_iter, added to the loss only for i > (run_lushnerf.py:629, 658-659)
-                w = 1e-2 if i > self.noisenerf_start_iter else 0.0
-                if step_prec is not self.model.precision:
-                    self._pack_weights()      # (the aligned-pixel march runs in the model's own kernel variant: other fragment copies)
-                loss = loss + w * self._consistency(consist, w)
-        finally:
-            hooks.sink, hooks.packed, hooks.live_acc = sink_before, None, acc_before
-        if not dense and self._live_mode():
-            self._live_snapshot(acc_before)      # (the caller's accumulator when it supplied one: the policy sees those steps too)
+        for a in range(0, N, mb):
+            b = min(a + mb, N)
+            part = self._fwd_bwd(batch, a, b, i, draws, (b - a) / N, force_naive)
+            loss = part if loss is None else loss + part
+        return loss
+
+    def _active_mask(self, force_naive: bool) -> int:
+        active = [True, not force_naive, False]
+        return sum(1 << s for s, (a, b) in enumerate(self.flat.segments) if active[s] and b > a)
+
+    def _update(self, mask: int, state: Optional[torch.Tensor] = None, calls: int = 0, fused: bool = True):
+        """Adam on the segments of `mask`; `fused`: ONE launch for all of them where the segments lie one after the other.
+        Host form (state None): the step's one collective, then rate and step counts from the host's counters, which it
+        advances; honours the _adam test seam.  Device form: rate and step counts from the device step state, which the
+        last launch advances by one step of `calls` lush_draws calls (the host's counters are the caller's to advance)."""
+        f, scale = self.flat, 1.0 / self.world
+        segs = [(s, a, b) for s, (a, b) in enumerate(f.segments) if (mask >> s) & 1]
+        ends = [b for _, b in f.segments]
+        fused = fused and self._segments_consecutive
+        if state is not None:
+            if fused:
+                ops.adam_step_state_multi(f.param, f.grad, self.m, self.v, ends, state, mask, grad_scale=scale)
+            else:
+                for s, a, b in segs:
+                    ops.adam_step_state(f.param[a:b], f.grad[a:b], self.m[a:b], self.v[a:b], state, s, grad_scale=scale)
+            ops.lib.call("lush_step_state_advance", ops.lib.ptr(state), int(calls), int(mask), float(self.lrate),
+                         float(self.lrate_decay * 1000), 0.9, 0.999, ops._stream())
+            return
         if self.distributed:
             self._all_reduce()          # RCCL sum over xGMI; the 1/world mean is folded into Adam
         lr = self.lr() if self._lr_next is None else self._lr_next
         self._lr_next = None
-        active = [True, not force_naive, False]
-        for s, (a, b) in enumerate(self.flat.segments):
-            if active[s] and b > a:
-                self.steps[s] += 1
-        if self._segments_consecutive and self._adam is ops.adam_step:
-            mask = sum(1 << s for s, (a, b) in enumerate(self.flat.segments) if active[s] and b > a)
-            ops.adam_step_multi(self.flat.param, self.flat.grad, self.m, self.v, [b for _, b in self.flat.segments], mask, lr, self.steps,
-                                grad_scale=1.0 / self.world)
+        for s, _, _ in segs:
+            self.steps[s] += 1
+        if fused and self._adam is ops.adam_step:
+            ops.adam_step_multi(f.param, f.grad, self.m, self.v, ends, mask, lr, self.steps, grad_scale=scale)
         else:
-            for s, (a, b) in enumerate(self.flat.segments):
-                if active[s] and b > a:
-                    self._adam(self.flat.param[a:b], self.flat.grad[a:b], self.m[a:b], self.v[a:b], lr, self.steps[s],
-                               grad_scale=1.0 / self.world)
+            for s, a, b in segs:
+                self._adam(f.param[a:b], f.grad[a:b], self.m[a:b], self.v[a:b], lr, self.steps[s], grad_scale=scale)
         self.global_step += 1
+
+    def step(self, batch: Dict[str, torch.Tensor], i: int, draws=None, consist: Optional[dict] = None, _dense=_ASK):
+        """One optimisation step on a batch {rays [N,3,2] (or c2w/view/px/py for device-side ray generation),
+        images_idx [N,1], target [N,3], fq_mask [N]}."""
+        self.model.train()
+        force_naive = i < self.kernel_start_iter
+        mb = self._micro(batch["target"].shape[0])
+        dense = self._backward_choice(mb, force_naive) if _dense is _ASK else _dense
+        self._eager_seen.add(dense)
+        hooks, own = self.model.hooks, self.model.precision
+        step_prec = self._step_precision(mb, force_naive, dense)
+        acc = self.live.acc if hooks.live_acc is None else hooks.live_acc
+        with self._stepping(step_prec, live_acc=acc):
+            loss = self._grads(batch, i, force_naive, draws)
+            if consist is not None and i >= self.noisenerf_start_iter:
+                # computed from i >= noisenerf_start_iter, added to the loss only for i > (run_lushnerf.py:629, 658-659)
+                w = 1e-2 if i > self.noisenerf_start_iter else 0.0
+                self.model.precision = own    # the aligned-pixel march runs in the model's own kernel variant ...
+                if step_prec is not own:
+                    self._pack_weights()      # (... other fragment copies)
+                loss = loss + w * self._consistency(consist, w)
+        if dense is False:
+            self.live.snapshot(acc)      # (the caller's accumulator when it supplied one: the policy sees those steps too)
+        self._update(self._active_mask(force_naive))
         return loss
 
     # ------------------------------------------------------------------ BASELINE config 1: the coarse-only step
@@ -465,36 +541,17 @@ class Trainer:
         after a replay.  Returns (loss, tone-mapped colours)."""
         model, hooks = self.model, self.model.hooks
         model.train()
-        sink_before, hooks.sink = hooks.sink, True
-        if state is not None:
-            hooks.state, hooks.draw_delta = state, 0
-        try:
-            with self._PrecisionFor(model, self._step_precision(batch["target"].shape[0], True, coarse_only=True)):
-                self._pack_weights(zero_grad=True)        # one launch: every network re-packed, the flat gradient cleared
-                rays = batch["rays"] if "rays" in batch else ops.gen_rays(batch["c2w"], batch["view"], batch["px"], batch["py"], self.K)
-                (rgb, depth, acc, extras), noise = model.render_infer(
-                    self.H, self.W, self.K, self.chunk, rays=rays, retraw=True, draws=draws, **dict(self.kw, N_importance=0))
-                tm = model.tonemapping(rgb)
-                loss, g, _ = ops.train_loss_grads(tm, tm, batch["target"], 1.0, work=self._loss_work)      # (a is b: rgb0 = rgb)
-                tm.backward(g)
+        fields = {} if state is None else dict(state=state, draw_delta=0)
+        with self._stepping(self._step_precision(batch["target"].shape[0], True, coarse_only=True), **fields):
+            self._pack_weights(zero_grad=True)        # one launch: every network re-packed, the flat gradient cleared
+            rays = batch["rays"] if "rays" in batch else ops.gen_rays(batch["c2w"], batch["view"], batch["px"], batch["py"], self.K)
+            (rgb, depth, acc, extras), noise = model.render_infer(
+                self.H, self.W, self.K, self.chunk, rays=rays, retraw=True, draws=draws, **dict(self.kw, N_importance=0))
+            tm = model.tonemapping(rgb)
+            loss, g, _ = ops.train_loss_grads(tm, tm, batch["target"], 1.0, work=self._loss_work)      # (a is b: rgb0 = rgb)
+            tm.backward(g)
             calls = self._coarse_only_calls = hooks.draw_delta      # lush_draws calls of this step (graph-body form)
-        finally:
-            hooks.sink, hooks.packed, hooks.state = sink_before, None, None
-        a0, a1 = self.flat.segments[0]
-        if state is not None:
-            ops.adam_step_state(self.flat.param[a0:a1], self.flat.grad[a0:a1], self.m[a0:a1], self.v[a0:a1], state, 0,
-                                grad_scale=1.0 / self.world)
-            ops.lib.call("lush_step_state_advance", ops.lib.ptr(state), int(calls), 1, float(self.lrate), float(self.lrate_decay * 1000),
-                         0.9, 0.999, ops._stream())
-        else:
-            if self.distributed:
-                self._all_reduce()
-            lr = self.lr() if self._lr_next is None else self._lr_next
-            self._lr_next = None
-            self.steps[0] += 1
-            ops.adam_step(self.flat.param[a0:a1], self.flat.grad[a0:a1], self.m[a0:a1], self.v[a0:a1], lr, self.steps[0],
-                          grad_scale=1.0 / self.world)
-            self.global_step += 1
+        self._update(1, state, calls, fused=False)      # (one segment: the single-segment launch)
         return loss, tm.detach()
 
     def capture_coarse_only(self, batch):
@@ -503,12 +560,10 @@ class Trainer:
         graph and advances the host's mirror of the counters; replay.loss / replay.tm are the graph's output tensors."""
         if self.world > 1:
             raise NotImplementedError("capture_coarse_only: one rank (the collective is not captured; use step_coarse_only)")
-        state = torch.zeros(ops.lib.load().lush_step_state_bytes(), dtype=torch.uint8, device=self.flat.param.device)
-        self._state_init(state)
-        static = batch.clone_static() if isinstance(batch, BlobBatch) else {k: v.clone() for k, v in batch.items()}
+        cap = self._new_capture(None, batch)
         graph = torch.cuda.CUDAGraph()
         with torch.cuda.graph(graph):
-            loss, tm = self.step_coarse_only(static, state=state)
+            loss, tm = self.step_coarse_only(cap.static, state=cap.state)
         hooks, calls = self.model.hooks, self._coarse_only_calls
 
         def replay():
@@ -516,8 +571,8 @@ class Trainer:
             self.steps[0] += 1
             self.global_step += 1
             hooks.draw_offset += calls      # (one lush_draws call per step: the march's; the noise branch draws nothing)
-        replay.loss, replay.tm, replay.graph, replay.state = loss, tm, graph, state
-        return replay, static
+        replay.loss, replay.tm, replay.graph, replay.state = loss, tm, graph, cap.state
+        return replay, cap.static
 
     # ------------------------------------------------------------------ the step as one HIP graph
     def _all_reduce(self):
@@ -531,42 +586,6 @@ class Trainer:
             ev[1].record()
             self.allreduce_events.append(ev)
 
-    def _body_grads(self, batch, i, force_naive, state, dense=False):
-        """First half of what step() enqueues -- zero the flat gradient, forward + backward of every micro-batch -- with the
-        Philox draw counter taken from the device step state."""
-        N = batch["target"].shape[0]
-        mb = self.micro_batch if 0 < self.micro_batch < N else N
-        loss = None
-        hooks = self.model.hooks
-        sink_before, hooks.sink = hooks.sink, True
-        hooks.state, hooks.draw_delta = state, 0
-        try:
-            with self._PrecisionFor(self.model, self._step_precision(mb, force_naive, dense=dense)):
-                self._pack_weights(zero_grad=True)
-                for a in range(0, N, mb):
-                    b = min(a + mb, N)
-                    part = self._fwd_bwd(batch, a, b, i, None, (b - a) / N, force_naive)
-                    loss = part if loss is None else loss + part
-        finally:
-            hooks.sink, hooks.state, hooks.packed = sink_before, None, None
-        return loss, hooks.draw_delta
-
-    def _body_update(self, force_naive, state, calls):
-        """Second half: Adam on the active segments with rate / step counts from the device step state, then advance it."""
-        active = [True, not force_naive, False]
-        mask = sum(1 << s for s, (a, b) in enumerate(self.flat.segments) if active[s] and b > a)
-        ends = [b for _, b in self.flat.segments]
-        if self._segments_consecutive:
-            ops.adam_step_state_multi(self.flat.param, self.flat.grad, self.m, self.v, ends, state, mask, grad_scale=1.0 / self.world)
-        else:
-            for s, (a, b) in enumerate(self.flat.segments):
-                if active[s] and b > a:
-                    ops.adam_step_state(self.flat.param[a:b], self.flat.grad[a:b], self.m[a:b], self.v[a:b], state, s,
-                                        grad_scale=1.0 / self.world)
-        ops.lib.call("lush_step_state_advance", ops.lib.ptr(state), int(calls), int(mask), float(self.lrate),
-                     float(self.lrate_decay * 1000), 0.9, 0.999, ops._stream())
-        return mask
-
     def _state_init(self, state):
         """(Re-)write the device step state from the host's counters: what the graph's kernels read instead of arguments."""
         hooks = self.model.hooks
@@ -574,6 +593,34 @@ class Trainer:
         ops.lib.call("lush_step_state_init", ops.lib.ptr(state), ops.C.c_ulonglong(hooks.draw_offset), int(self.global_step), steps,
                      float(self.lrate), float(self.lrate_decay * 1000), 0.9, 0.999, ops._stream())
         return (int(hooks.draw_offset), int(self.global_step), tuple(self.steps))
+
+    def _new_capture(self, key, batch) -> _Capture:
+        """What a capture starts from: a device step state written from the host's counters, and the graph's own copy of the batch."""
+        state = torch.zeros(ops.lib.load().lush_step_state_bytes(), dtype=torch.uint8, device=self.flat.param.device)
+        mirror = self._state_init(state)
+        static = batch.clone_static() if isinstance(batch, BlobBatch) else {k: v.clone() for k, v in batch.items()}
+        return _Capture(key, static, state, mirror)
+
+    def _capture_step(self, G: _Capture, i, force_naive, mb, dense, split) -> _CapturedStep:
+        """The step with one backward choice, captured: what step() enqueues, with the Philox draw counter, the rate and Adam's step
+        counts taken from the device step state -- as one graph, or (split) as two around the collective, which is not captured."""
+        self.model.train()
+        hooks = self.model.hooks
+        acc = self.live.acc if hooks.live_acc is None else hooks.live_acc
+        mask = self._active_mask(force_naive)
+        g1, g2 = torch.cuda.CUDAGraph(), None
+        with torch.cuda.graph(g1, **({} if G.pool is None else dict(pool=G.pool))):      # (the captured steps never run at once: one pool)
+            with self._stepping(self._step_precision(mb, force_naive, dense), live_acc=acc, state=G.state, draw_delta=0):
+                loss = self._grads(G.static, i, force_naive)
+                calls = hooks.draw_delta
+            if not split:
+                self._update(mask, G.state, calls)
+        if split:
+            g2 = torch.cuda.CUDAGraph()
+            with torch.cuda.graph(g2, pool=g1.pool()):
+                self._update(mask, G.state, calls)
+        G.pool = g1.pool()
+        return _CapturedStep(g1, g2, loss, calls, mask, acc)
 
     def invalidate_graph(self):
         """Forget the captured step (checkpoint load, replica sync: parameters, moments and counters were rewritten)."""
@@ -602,70 +649,44 @@ class Trainer:
         prec = self.model.precision
         key = (force_naive, allk, split, prec.fwd, prec.bwd, prec.variant,
                tuple(sorted((k, tuple(v.shape), v.dtype) for k, v in batch.items())))
-        if self._graph is not None and self._graph["key"] != key:
+        if self._graph is not None and self._graph.key != key:
             self.invalidate_graph()         # (e.g. force_naive flips at kernel_start_iter: the RBK / noise kernels' first call must be eager)
         if self._lr_next is not None or i >= self.noisenerf_start_iter or consist is not None or self._graph_eager_left > 0 \
                 or not self.flat.param.is_cuda:
             self._graph_eager_left = max(self._graph_eager_left - 1, 0)
             return self.step(batch, i, consist=consist)      # (the consistency branch draws its anchor / pixels on the host: eager)
         hooks = self.model.hooks
-        N = batch["target"].shape[0]
-        dense = self._backward_choice(self.micro_batch if 0 < self.micro_batch < N else N, force_naive)
+        mb = self._micro(batch["target"].shape[0])
+        dense = self._backward_choice(mb, force_naive)
         if dense not in self._eager_seen:             # (each backward's first step is a real, eager one: its lazy initialisation)
             return self.step(batch, i, _dense=dense)
-        if self._graph is None or dense not in self._graph["sub"]:
-            self.model.train()
-            dev = self.flat.param.device
-            if self._graph is None:
-                state = torch.zeros(ops.lib.load().lush_step_state_bytes(), dtype=torch.uint8, device=dev)
-                mirror = self._state_init(state)
-                static = batch.clone_static() if isinstance(batch, BlobBatch) else {k: v.clone() for k, v in batch.items()}
-                self._graph = dict(key=key, static=static, state=state, mirror=mirror, sub={}, pool=None)
-            G = self._graph
-            state, static = G["state"], G["static"]
-            g1 = torch.cuda.CUDAGraph()
-            g2 = None
-            pool = {} if G["pool"] is None else dict(pool=G["pool"])      # (the two captured steps never run at once: one pool)
-            distributed, self.distributed = self.distributed, False      # (the captured body never calls the collective itself)
-            acc_before, hooks.live_acc = hooks.live_acc, (self._live_cum if hooks.live_acc is None else hooks.live_acc)
-            try:
-                if not split:
-                    with torch.cuda.graph(g1, **pool):
-                        loss, calls = self._body_grads(static, i, force_naive, state, dense)
-                        mask = self._body_update(force_naive, state, calls)
-                else:
-                    with torch.cuda.graph(g1, **pool):
-                        loss, calls = self._body_grads(static, i, force_naive, state, dense)
-                    g2 = torch.cuda.CUDAGraph()
-                    with torch.cuda.graph(g2, pool=g1.pool()):
-                        mask = self._body_update(force_naive, state, calls)
-            finally:
-                self.distributed, hooks.live_acc = distributed, acc_before
-            G["pool"] = g1.pool()
-            G["sub"][dense] = dict(g1=g1, g2=g2, loss=loss, calls=calls, mask=mask)
+        if self._graph is None:
+            self._graph = self._new_capture(key, batch)
         G = self._graph
-        sub = G["sub"][dense]
-        if G["mirror"] != (int(hooks.draw_offset), int(self.global_step), tuple(self.steps)):
-            G["mirror"] = self._state_init(G["state"])
-        if isinstance(batch, BlobBatch) and isinstance(G["static"], BlobBatch):
-            G["static"].load(batch)                  # one device copy for all per-step inputs
+        if dense not in G.sub:
+            G.sub[dense] = self._capture_step(G, i, force_naive, mb, dense, split)
+        sub = G.sub[dense]
+        if G.mirror != (int(hooks.draw_offset), int(self.global_step), tuple(self.steps)):
+            G.mirror = self._state_init(G.state)
+        if isinstance(batch, BlobBatch) and isinstance(G.static, BlobBatch):
+            G.static.load(batch)                     # one device copy for all per-step inputs
         else:
             for k, v in batch.items():
-                G["static"][k].copy_(v, non_blocking=True)
-        sub["g1"].replay()
-        if sub["g2"] is not None:
+                G.static[k].copy_(v, non_blocking=True)
+        sub.g1.replay()
+        if sub.g2 is not None:
             if self.distributed:
                 self._all_reduce()
-            sub["g2"].replay()
-        if not dense:
-            self._live_snapshot()                    # (the captured live-point march adds its counts on the device)
+            sub.g2.replay()
+        if dense is False:
+            self.live.snapshot(sub.acc)              # (the captured live-point march adds its counts on the device, to the accumulator it was captured with)
         for s in range(3):
-            if (sub["mask"] >> s) & 1:
+            if (sub.mask >> s) & 1:
                 self.steps[s] += 1
         self.global_step += 1
-        hooks.draw_offset += sub["calls"]
-        G["mirror"] = (int(hooks.draw_offset), int(self.global_step), tuple(self.steps))
-        return sub["loss"]
+        hooks.draw_offset += sub.calls
+        G.mirror = (int(hooks.draw_offset), int(self.global_step), tuple(self.steps))
+        return sub.loss
 
     def faults(self) -> int:
         """Numerical-fault word of the model's render calls since the last read (one device sync; the reference

@@ -492,7 +492,7 @@ def test_checkpoint_interop_with_reference_layout(tmp_path):
     tr.m.copy_(torch.from_numpy(synth.normal((tr.m.numel(),), 1)))
     tr.v.copy_(torch.from_numpy(synth.uniform((tr.v.numel(),), 0, 1, 2)))
     path = str(tmp_path / "000007.tar")
-    tr._dense_now, tr._dense_steps, tr.live_share = True, 5, 0.73          # where the live-point policy stands (round 6: saved too)
+    tr.live.dense_now, tr.live.dense_steps, tr.live_share = True, 5, 0.73          # where the live-point policy stands (round 6: saved too)
     CK.save_checkpoint(path, net, 7, tr)
     ck = torch.load(path, weights_only=False)
     # the reference's three keys (all its loader reads, run_lushnerf.py:373-389) + one of ours it never looks at
@@ -519,7 +519,7 @@ def test_checkpoint_interop_with_reference_layout(tmp_path):
     for (k, a), (_, b) in zip(net.state_dict().items(), net2.state_dict().items()):
         assert torch.equal(a, b), k
     assert tr2.steps == [7, 5, 0] and tr2.global_step == 7
-    assert (tr2._dense_now, tr2._dense_steps, tr2.live_share, tr2._live_snaps) == (True, 5, 0.73, [])      # a resumed run chooses as the uninterrupted one
+    assert (tr2.live.dense_now, tr2.live.dense_steps, tr2.live_share, tr2.live.in_flight) == (True, 5, 0.73, [])      # a resumed run chooses as the uninterrupted one
     a, b = tr.flat.segments[1]
     assert torch.equal(tr2.m[:b], tr.m[:b]) and torch.equal(tr2.v[:b], tr.v[:b])
     # the reference resumes with the rate its optimizer was saved with (lr of global_step 7), for one step
@@ -535,9 +535,9 @@ def test_checkpoint_interop_with_reference_layout(tmp_path):
     assert len(opt2.state) == 0
     net3, tr3 = _small_trainer(5)
     tr3.m.fill_(1.0); tr3.steps = [4, 4, 0]
-    tr3._dense_now, tr3.live_share = True, 0.9
+    tr3.live.dense_now, tr3.live_share = True, 0.9
     assert CK.load_checkpoint(path2, net3, tr3) == 9
-    assert (tr3._dense_now, tr3.live_share) == (False, None)                   # a file without the key: the policy starts over
+    assert (tr3.live.dense_now, tr3.live_share) == (False, None)                   # a file without the key: the policy starts over
     assert tr3.global_step == 9 and tr3.steps == [0, 0, 0] and float(tr3.m.abs().max()) == 0.0
 
 
@@ -658,75 +658,135 @@ def test_quoted_numbers_match_their_sources():
 
 
 def test_live_point_policy_state_machine():
-    """Trainer._dense_backward_now (no GPU: the decision logic alone): live until a share arrives; dense above LIVE_MAX_SHARE with one
-    live probe every LIVE_PROBE_EVERY steps; back to live below LIVE_MIN_SHARE (hysteresis); "live" / "dense" override."""
-    from lush_nerf_amd.trainer import Trainer
-    t = Trainer.__new__(Trainer)
-    t.live_policy, t.live_share, t._dense_now, t._dense_steps = "auto", None, False, 0
-    t.LIVE_PROBE_EVERY = 4
-    assert t._dense_backward_now() is False                      # nothing known yet
-    t.live_share = 0.5
-    assert t._dense_backward_now() is False
-    t.live_share = 0.9
-    seq = [t._dense_backward_now() for _ in range(9)]
+    """LivePolicy.decide (no GPU: the decision logic alone): live until a share arrives; dense above MAX_SHARE with one
+    live probe every PROBE_EVERY steps; back to live below MIN_SHARE (hysteresis); "live" / "dense" override."""
+    from lush_nerf_amd.trainer import LivePolicy
+    t = LivePolicy("cpu")
+    assert (t.mode, t.share, t.dense_now, t.dense_steps) == ("auto", None, False, 0)
+    t.PROBE_EVERY = 4
+    assert t.decide() is False                                    # nothing known yet
+    t.share = 0.5
+    assert t.decide() is False
+    t.share = 0.9
+    seq = [t.decide() for _ in range(9)]
     assert seq == [True, True, True, True, False, True, True, True, False], seq      # every fourth dense step is a live probe
-    assert (t.LIVE_MIN_SHARE, t.LIVE_MAX_SHARE) == (0.65, 0.70)   # inside the measured break-even band 0.69 .. 0.76 (profiles/r05_live_points.md)
-    t.live_share = 0.67                                           # between MIN and MAX: stays dense
-    assert t._dense_backward_now() is True
-    t.live_share = 0.5
-    assert t._dense_backward_now() is False and t._dense_now is False
-    t.live_share = 0.67                                           # ... and stays live until it exceeds MAX again
-    assert t._dense_backward_now() is False
-    t.live_policy, t.live_share = "dense", 0.1
-    assert t._dense_backward_now() is True
-    t.live_policy, t.live_share = "live", 0.99
-    assert t._dense_backward_now() is False
+    assert (t.MIN_SHARE, t.MAX_SHARE) == (0.65, 0.70)             # inside the measured break-even band 0.69 .. 0.76 (profiles/r05_live_points.md)
+    t.share = 0.67                                                # between MIN and MAX: stays dense
+    assert t.decide() is True
+    t.share = 0.5
+    assert t.decide() is False and t.dense_now is False
+    t.share = 0.67                                                # ... and stays live until it exceeds MAX again
+    assert t.decide() is False
+    t.mode, t.share = "dense", 0.1
+    assert t.decide() is True
+    t.mode, t.share = "live", 0.99
+    assert t.decide() is False
+
+
+class _Event:
+    """Stands in for torch.cuda.Event in a LivePolicy on CPU tensors."""
+    made = []
+
+    def __init__(self):
+        self.recorded = self.waited = False
+        _Event.made.append(self)
+
+    def record(self):
+        self.recorded = True
+
+    def synchronize(self):
+        assert self.recorded
+        self.waited = True
 
 
 def test_live_point_policy_reads_a_fixed_lag():
-    """The choice for step n is taken from the counts of step n - LIVE_LAG, whatever has or has not arrived: _live_poll WAITS for that
+    """The choice for step n is taken from the counts of step n - LAG, whatever has or has not arrived: choose() WAITS for that
     snapshot (event.synchronize) and leaves younger ones alone, so a seeded run makes the same choices every time (advisor, round 5:
     event.query() made them depend on host / device timing).  Counts a caller accumulated in a buffer of its own start a new series
-    instead of being subtracted from the trainer's."""
-    from lush_nerf_amd.trainer import Trainer
+    instead of being subtracted from the policy's -- and the policy's own series goes on where it was when its accumulator returns
+    (the parent started it over from zero: 160 / 600 instead of 40 / 200)."""
+    from lush_nerf_amd.trainer import LivePolicy
+    t = LivePolicy("cpu", event=_Event)
+    t.mode = "live"                                                # (the readings are the subject: every step is a live one)
+    evs = _Event.made = []
+    other = torch.zeros(4, dtype=torch.int64)                      # a caller's accumulator
 
-    class Ev:
-        def __init__(self):
-            self.waited = False
+    def snap(counts, acc=None):
+        (t.acc if acc is None else acc).copy_(torch.tensor(counts))
+        assert t.snapshot(acc) is True and t.in_flight[-1][2] == t.step
 
-        def synchronize(self):
-            self.waited = True
+    assert t.choose() is False and t.step == 1
+    snap([40, 100, 10, 100])
+    t.choose()
+    assert t.step == 2 and t.share is None and not evs[0].waited   # step 1's counts are not step 2's business yet
+    snap([100, 200, 20, 200])
+    t.choose()
+    assert t.step == 3 and evs[0].waited and not evs[1].waited and t.share == 0.25      # step 3 decides on step 1: (40 + 10) / 200
+    t.choose()
+    assert t.step == 4 and evs[1].waited and t.share == (60 + 10) / 200
+    snap([5, 10, 5, 10], acc=other)                                # a caller's accumulator: a new series from zero, no negative delta
+    t.choose()
+    snap([15, 20, 15, 20], acc=other)
+    t.choose()
+    assert t.step == 6 and t.share == 0.5 and other.data_ptr() in t._prev and not evs[3].waited
+    t.choose()
+    assert t.step == 7 and t.share == 1.0 and not t.in_flight
+    t.choose()
+    snap([130, 300, 30, 300])                                      # the policy's own accumulator again: on from [100, 200, 20, 200]
+    t.choose()
+    t.choose()
+    assert t.step == 10 and t.share == (30 + 10) / (100 + 100) and not t.in_flight
+    assert set(t._prev) == {t.acc.data_ptr()}                      # (one caller's reading is kept at the most: a fresh tensor per step is fine)
 
-    t = Trainer.__new__(Trainer)
-    t._live_ring = torch.zeros(8, 4, dtype=torch.int64)
-    t._live_snaps, t._live_prev, t._live_prev_acc, t._live_step, t.live_share = [], [0, 0, 0, 0], 111, 0, None
-    evs = []
 
-    def snap(step, counts, acc=111):
-        row = len(evs) % 8
-        t._live_ring[row] = torch.tensor(counts)
-        evs.append(Ev())
-        t._live_snaps.append((evs[-1], row, step, acc))
+def test_live_point_policy_keeps_at_most_lag_plus_one_snapshot_in_flight():
+    """A snapshot is enqueued for exactly the steps whose choice the policy took and answered "live", once: 100 rounds of "take the
+    choice, snapshot if live" at a share above MAX_SHARE (dense steps and probes) never leave more than LAG + 1 in flight and never
+    have a snapshot refused; a request on behalf of a step the policy was not asked about (a small launch: the parent filled the
+    ring with those and then dropped the first counted step's) leaves nothing behind."""
+    from lush_nerf_amd.trainer import LivePolicy
+    t = LivePolicy("cpu", event=_Event)
+    t.PROBE_EVERY = 4
+    assert t.snapshot() is False and not t.in_flight               # before any choice
+    chosen = []
+    for n in range(100):
+        if n % 7 == 3:                                             # a step that does not consult the policy
+            before = list(t.in_flight)
+            assert t.snapshot() is False and t.in_flight == before
+            continue
+        chosen.append(t.choose())
+        if not chosen[-1]:
+            t.acc += torch.tensor([90, 100, 95, 100])              # a live march: 185 of 200 points live
+            assert t.snapshot() is True                            # never refused ...
+            assert t.snapshot() is False                           # ... and one per step
+        assert len(t.in_flight) <= t.LAG + 1
+    # live until step 1's share arrives at step 3, then dense with every fourth dense step a live probe
+    assert chosen == [False, False, True] + [k % 4 != 0 for k in range(1, len(chosen) - 2)], chosen
+    assert t.share == 0.925 and t.step == len(chosen) == 86
 
-    snap(1, [40, 100, 10, 100])
-    t._live_step = 2
-    t._live_poll()
-    assert t.live_share is None and not evs[0].waited            # step 1's counts are not step 2's business yet
-    snap(2, [100, 200, 20, 200])
-    t._live_step = 3
-    t._live_poll()
-    assert evs[0].waited and not evs[1].waited and t.live_share == 0.25      # step 3 decides on step 1: (40 + 10) / 200
-    t._live_step = 4
-    t._live_poll()
-    assert evs[1].waited and t.live_share == (60 + 10) / 200
-    snap(4, [5, 10, 5, 10], acc=222)                               # a caller's accumulator: a new series from zero, no negative delta
-    t._live_step = 6
-    t._live_poll()
-    assert t.live_share == 0.5 and t._live_prev_acc == 222
-    snap(5, [15, 20, 15, 20], acc=222)
-    t._live_step = 7
-    t._live_poll()
-    assert t.live_share == 1.0 and not t._live_snaps
+
+def test_live_point_policy_restore_starts_over_from_the_present_counts():
+    """LivePolicy.load_state (checkpoint load): the snapshots in flight are dropped, the step counter restarts and the accumulator's
+    present value is the previous reading, so the first share after a restore covers the steps after it only."""
+    from lush_nerf_amd.trainer import LivePolicy
+    t = LivePolicy("cpu", event=_Event)
+    for counts in ([40, 100, 10, 100], [100, 200, 20, 200]):
+        t.choose()
+        t.acc.copy_(torch.tensor(counts))
+        assert t.snapshot()
+    assert len(t.in_flight) == 2 and t.step == 2
+    t.load_state({"policy": "dense", "dense_now": False, "dense_steps": 3, "live_share": 0.5})
+    assert t.in_flight == [] and t.step == 0 and t.counts() == [100, 200, 20, 200]
+    assert t.state() == {"policy": "auto", "dense_now": False, "dense_steps": 3, "live_share": 0.5}      # (the caller's own mode stays)
+    t.choose()
+    t.acc += torch.tensor([30, 100, 30, 100])
+    assert t.snapshot()
+    t.choose()
+    assert t.share == 0.5
+    t.choose()
+    assert t.step == 3 and t.share == 60 / 200
+    t.load_state(None)                                             # a file without the key: the policy starts over
+    assert (t.dense_now, t.dense_steps, t.share, t.step, t.in_flight) == (False, 0, None, 0, [])
 
 
 def test_kernel_sources_have_one_compile_time_form():

@@ -727,7 +727,7 @@ if rank == 0:
     print(f"2 ranks vs 1 rank on the concatenated batch: gradient {eg:.1e}, parameters {ep:.1e}", flush=True)
     assert eg < 2e-4 and ep < 1e-5, (eg, ep)
     del tr1, net1
-# Ranks that CHOOSE DIFFERENTLY (the live-point policy decides per rank, from its own live share: trainer.py _dense_backward_now):
+# Ranks that CHOOSE DIFFERENTLY (the live-point policy decides per rank, from its own live share: trainer.py LivePolicy.decide):
 # rank 0 runs the live-point backward, rank 1 the backward over all the points, in the headline mode.  Both forms add into the
 # same flat gradient and every step holds exactly one collective, so: no hang, replicas identical after every step, and the pair
 # still equals one rank on the concatenated batch.
@@ -754,7 +754,7 @@ pix = [{k: torch.from_numpy(v).to(dev) for k, v in synth.ray_batch(N, 200 + 2 * 
 for s in range(6):
     tr2.step_graph(pix[s], 1 + s)
     assert tr2.replica_checksum() == 0.0, s
-assert tr2._graph is not None and list(tr2._graph["sub"]) == [rank == 1], (rank, tr2._graph and list(tr2._graph["sub"]))
+assert tr2._graph is not None and list(tr2._graph.sub) == [rank == 1], (rank, tr2._graph and list(tr2._graph.sub))
 assert bool(torch.isfinite(tr2.flat.param).all()) and tr2.faults() == 0
 dist.barrier()
 dist.destroy_process_group()
@@ -961,7 +961,7 @@ def test_step_graph_resynchronises_with_the_host(diag, mode, tmp_path):
                 lb.append(float(B.step(b, s)))
             else:
                 lb.append(float(B.step_graph(b, s, split=(mode == "split"))))
-        assert B._graph is not None and all((g["g2"] is not None) == (mode == "split") for g in B._graph["sub"].values())
+        assert B._graph is not None and all((g.g2 is not None) == (mode == "split") for g in B._graph.sub.values())
         assert A.steps == B.steps and A.global_step == B.global_step and A.model.hooks.draw_offset == B.model.hooks.draw_offset
         worst = max(abs(x - y) / abs(x) for x, y in zip(la, lb))
         assert worst < 2e-5, (mode, worst, la, lb)
@@ -1459,9 +1459,9 @@ def test_live_point_march_in_the_other_modes(diag, mode, n):
 
 
 def test_trainer_falls_back_to_the_dense_backward_when_most_points_are_live(diag):
-    """The live-point march costs one forward over all the points more than the dense one: while more than Trainer.LIVE_MAX_SHARE
-    of the points are live the trainer runs the dense backward (and looks again every LIVE_PROBE_EVERY steps); the share arrives
-    through pinned snapshots, nothing blocks."""
+    """The live-point march costs one forward over all the points more than the dense one: while more than LivePolicy.MAX_SHARE
+    of the points are live the trainer runs the dense backward (and looks again every PROBE_EVERY steps); the share arrives
+    through pinned snapshots, the host waiting only for the one LAG steps back."""
     from lush_nerf_amd import ops, synth
     from lush_nerf_amd.trainer import Trainer
     dev = torch.device("cuda:0")
@@ -1470,7 +1470,7 @@ def test_trainer_falls_back_to_the_dense_backward_when_most_points_are_live(diag
         net.mlp_coarse.alpha_linear.bias.fill_(6.0)
         net.mlp_fine.alpha_linear.bias.fill_(6.0)
     tr = Trainer(net, diag.H, diag.W, diag.F, 64, 64, kernel_start_iter=0, allkernel_start_iter=0, lrate=0.0)
-    tr.LIVE_PROBE_EVERY = 4
+    tr.live.PROBE_EVERY = 4
     b = {k: diag.gpu(v) for k, v in diag.batch_of(512, 5).items()}
     modes = []
     for i in range(12):
@@ -1494,7 +1494,7 @@ def test_trainer_falls_back_to_the_dense_backward_when_most_points_are_live(diag
             n2.mlp_coarse.alpha_linear.bias.fill_(6.0)
             n2.mlp_fine.alpha_linear.bias.fill_(6.0)
         t = Trainer(n2, diag.H, diag.W, diag.F, 64, 64, kernel_start_iter=0, allkernel_start_iter=0)
-        t.LIVE_PROBE_EVERY = 4
+        t.live.PROBE_EVERY = 4
         return t
     A, B = make(), make()
     la, lb, mb = [], [], []
@@ -1505,12 +1505,66 @@ def test_trainer_falls_back_to_the_dense_backward_when_most_points_are_live(diag
         lb.append(float(B.step_graph(b, i)))
         torch.cuda.synchronize()
         mb.append("live" if B.live_counts()[1] > before[1] else "dense")
-    assert B._graph is not None and set(B._graph["sub"]) == {False, True}, (B._graph and list(B._graph["sub"]), mb)
+    assert B._graph is not None and set(B._graph.sub) == {False, True}, (B._graph and list(B._graph.sub), mb)
     assert mb.count("live") >= 3 and mb.count("dense") >= 8, mb
     assert A.steps == B.steps and A.global_step == B.global_step and A.model.hooks.draw_offset == B.model.hooks.draw_offset
     worst = max(abs(x - y) / abs(x) for x, y in zip(la, lb))
     print(f"step_graph under the live / dense policy ({' '.join(m[0] for m in mb)}): losses within {worst:.1e} of sixteen eager steps")
     assert worst < 5e-5, (worst, la, lb)
+
+
+def _policy_trainer(diag):
+    """The headline mode at 64 + 64 samples with nearly every point live, as in the test above."""
+    from lush_nerf_amd import ops
+    from lush_nerf_amd.trainer import Trainer
+    net = diag._nerf_all(64, 5, sharp=False, precision=ops.Precision(ops.PLANES_F16, ops.PLANES_F16, 0), rbk_scale=2.0e4)
+    with torch.no_grad():
+        net.mlp_coarse.alpha_linear.bias.fill_(6.0)
+        net.mlp_fine.alpha_linear.bias.fill_(6.0)
+    return net, Trainer(net, diag.H, diag.W, diag.F, 64, 64, kernel_start_iter=0, allkernel_start_iter=0, lrate=0.0)
+
+
+def test_small_launch_steps_leave_no_snapshot_in_flight(diag):
+    """Steps the policy is not consulted for leave nothing behind: 16 rays x 5 sub-frames x 128 samples = 10 240 points run on the
+    small-launch kernels (at most SMALL_LAUNCH_POINTS), 64 rays = 40 960 points consult the policy.  After ten small steps nothing is
+    in flight, and the share of the first large step has arrived when the third one starts (LAG = 2).  (Before LivePolicy the small
+    steps filled the ring with rows nobody read, the first large step's snapshot was dropped and the share came one step later.)"""
+    net, tr = _policy_trainer(diag)
+    small = {k: diag.gpu(v) for k, v in diag.batch_of(16, 5).items()}
+    large = {k: diag.gpu(v) for k, v in diag.batch_of(64, 5).items()}
+    assert 16 * (net.mlp_rbk.num_motion + 1) * 128 == 10240 <= tr.SMALL_LAUNCH_POINTS < 64 * (net.mlp_rbk.num_motion + 1) * 128 == 40960
+    for i in range(10):
+        tr.step(small, i)
+    assert tr.live.in_flight == [] and tr.live.step == 0 and tr.live_share is None
+    for i in range(10, 13):
+        tr.step(large, i)
+        assert len(tr.live.in_flight) <= tr.live.LAG + 1
+    assert tr.live.step == 3 and tr.live_share is not None, (tr.live.step, tr.live_share)
+
+
+def test_captured_step_snapshots_the_accumulator_it_was_captured_with(diag):
+    """A caller's hooks.live_acc under step_graph: the captured march adds its counts to the caller's tensor, so that is the one the
+    policy must read after a replay (it read the trainer's own, which such a run never touches: the share stood still)."""
+    net, tr = _policy_trainer(diag)
+    tr.live_policy = "live"                                        # (every step a live one: replays of one captured step)
+    b = {k: diag.gpu(v) for k, v in diag.batch_of(64, 5).items()}
+    mine = torch.zeros(4, dtype=torch.int64, device=b["target"].device)
+    net.hooks.live_acc = mine
+    handed, snapshot = [], tr.live.snapshot
+
+    def recording(acc=None):
+        handed.append(acc)
+        return snapshot(acc)
+    tr.live.snapshot = recording
+    counts = []
+    for i in range(6):                                             # two eager steps, then the capture and four replays
+        tr.step_graph(b, i)
+        counts.append([int(x) for x in mine.tolist()])
+    assert tr._graph is not None and list(tr._graph.sub) == [False] and tr._graph.sub[False].acc is mine
+    assert len(handed) == 6 and all(a is mine for a in handed), handed
+    assert all(c1[1] > c0[1] and c1[3] > c0[3] for c0, c1 in zip(counts[1:], counts[2:])), counts      # grew across the replays
+    assert tr.live_counts() == [0, 0, 0, 0] and tr.live_share is not None and tr.live_share > 0.95, (tr.live_counts(), tr.live_share)
+    assert net.hooks.live_acc is mine
 
 
 def test_march_through_the_c_abi_alone(diag):
