@@ -95,7 +95,8 @@ int lush_composite_bwd_full(const float* raw, const float* z, const float* rays,
                             const float* noise, float noise_std, float near_mask, int white_bkgd,
                             const float* g_rgb, const float* g_density, const float* g_acc, const float* g_weights,
                             const float* g_depth, float* d_raw, float* d_z, float* d_rays_d, lush_stream_t stream);
-/* scale2 = {s, 1/s}: s = the power of two that puts max(block_max[0..n)) into [8, 16); 1 when the maximum is 0 or not finite
+/* scale2 = {s, 1/s}: s = the power of two that puts max(block_max[0..n)) into [8, 16), at most 2^126 (a maximum below 2^-122
+ * is scaled short of 8: s stays finite and 1/s a normal float); 1 when the maximum is 0 or not finite
  * (the rule of the loss-scaled fp16 gradient chain). */
 int lush_loss_scale(const float* block_max, int n, float* scale2, lush_stream_t stream);
 

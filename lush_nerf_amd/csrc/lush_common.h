@@ -141,6 +141,23 @@ __device__ __forceinline__ f32x16 mfma_planes(const bf16x8 (&a)[NS], const bf16x
 
 __host__ __device__ constexpr int mfma_per_product(int ns) { return ns == 1 ? 1 : (ns == 2 ? 3 : 6); }
 
+// The loss scale of the fp16 gradient chain from max|d_raw| (grad_scale_kernel and loss_scale_kernel: the one statement of the
+// rule): out = {s, 1/s}, s = 2^k the power of two that puts the maximum into [8, 16); 1 when the maximum is 0 or not finite.
+// k is capped at 126: below a maximum of 2^-122 the scaled maximum falls short of 8 instead of s reaching Inf (k = 128, from
+// 2^-124 down) or 1/s a subnormal that a flush turns into 0 (k = 127) -- Inf * d_raw * 0 made a step's gradients NaN.
+__device__ __forceinline__ void loss_scale_rule(float mx, float* __restrict__ out) {
+    float sc = 1.f, inv = 1.f;
+    if (mx > 0.f && mx < 3.0e38f) {
+        int e;
+        frexpf(mx, &e);                     // mx = f * 2^e, f in [0.5, 1)
+        const int k = 4 - e < 126 ? 4 - e : 126;      // (k >= -124: mx < 2^128)
+        sc = ldexpf(1.f, k);                // mx * sc in [8, 16) for mx >= 2^-122
+        inv = ldexpf(1.f, -k);
+    }
+    out[0] = sc;
+    out[1] = inv;
+}
+
 // wave64 reductions / scans -------------------------------------------------
 // By DPP (data-parallel primitives on the VALU: the other lane's value is an operand modifier), the sequence the compiler's own
 // wave scans use on gfx9: an inclusive scan inside each row of 16 lanes (row_shr 1, 2, 4, 8), then the row totals carried

@@ -214,14 +214,7 @@ __global__ __launch_bounds__(256) void loss_scale_kernel(const float* __restrict
     __syncthreads();
     if (threadIdx.x == 0) {
         const float mx = fmaxf(fmaxf(sm[0], sm[1]), fmaxf(sm[2], sm[3]));
-        float sc = 1.f;
-        if (mx > 0.f && mx < 3.0e38f) {
-            int e;
-            frexpf(mx, &e);                 // mx = f * 2^e, f in [0.5, 1)
-            sc = ldexpf(1.f, 4 - e);        // mx * sc in [8, 16)
-        }
-        scale2[0] = sc;
-        scale2[1] = 1.f / sc;
+        loss_scale_rule(mx, scale2);
     }
 }
 

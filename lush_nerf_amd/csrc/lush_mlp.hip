@@ -684,7 +684,10 @@ __global__ __launch_bounds__(NW * 64) void mlp_bwd_kernel(const MlpBwdArgs A) {
 #pragma unroll
             for (int p = 0; p < PARTS; ++p) s += dxbuf[(p * MT + pt) * 6 + c];
             const long long gpt = pt0 + pt;
-            if (gpt < A.P) A.dpts[gpt * 8 + (c < 3 ? c : c + 1)] = s;
+            if (gpt < A.P) {
+                A.dpts[gpt * 8 + (c < 3 ? c : c + 1)] = s;
+                if (c % 3 == 2) A.dpts[gpt * 8 + (c < 3 ? 3 : 7)] = 0.f;      // the pad columns are zeros, as the wide kernels write them (include/lush_march.h)
+            }
         }
         lds_barrier();
     }
@@ -1523,14 +1526,7 @@ __global__ __launch_bounds__(256) void grad_scale_kernel(const float* __restrict
         }
         if (last) {
             const float mx = gridDim.x == 1 ? m : __uint_as_float(atomicMax(work, 0u));
-            float sc = 1.f;
-            if (mx > 0.f && mx < 3.0e38f) {
-                int e;
-                frexpf(mx, &e);                 // mx = f * 2^e, f in [0.5, 1)
-                sc = ldexpf(1.f, 4 - e);        // mx * sc in [8, 16)
-            }
-            out[0] = sc;
-            out[1] = 1.f / sc;
+            loss_scale_rule(mx, out);
             work[0] = 0u;
             work[1] = 0u;
             __threadfence();

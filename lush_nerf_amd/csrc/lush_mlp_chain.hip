@@ -1076,7 +1076,10 @@ __global__ __launch_bounds__(CH_NT) void mlp_chain_bwd_kernel(const MlpBwdArgs A
 #pragma unroll
             for (int p = 0; p < PARTS; ++p) sum += dxbuf[(p * CH_MT + pt) * 6 + c];
             const long long gp = pt0 + pt;
-            if (gp < P) A.dpts[gp * 8 + (c < 3 ? c : c + 1)] = sum * ginv;
+            if (gp < P) {
+                A.dpts[gp * 8 + (c < 3 ? c : c + 1)] = sum * ginv;
+                if (c % 3 == 2) A.dpts[gp * 8 + (c < 3 ? 3 : 7)] = 0.f;      // the pad columns are zeros, as the wide kernels write them (include/lush_march.h)
+            }
         }
     }
     wait_vm<0>();
@@ -1328,7 +1331,10 @@ __global__ __launch_bounds__(CH_NT, 2) void mlp_chain_bwd_half_kernel(const MlpB
 #pragma unroll
             for (int p = 0; p < PARTS; ++p) sum += dxbuf[(p * CH_MT + pt) * 6 + c];
             const long long gp = pt0 + pt;
-            if (gp < P) A.dpts[gp * 8 + (c < 3 ? c : c + 1)] = sum * ginv;
+            if (gp < P) {
+                A.dpts[gp * 8 + (c < 3 ? c : c + 1)] = sum * ginv;
+                if (c % 3 == 2) A.dpts[gp * 8 + (c < 3 ? 3 : 7)] = 0.f;      // the pad columns are zeros, as the wide kernels write them (include/lush_march.h)
+            }
         }
     }
     wait_vm<0>();
